@@ -11,10 +11,27 @@ N GPUs (one process per GPU, torch.distributed.run): every rank reduces its
 own 8 x 256 MiB shard (the path shards by chunk; no data-path collective), so
 scaling is weak and value = N x 2.25 GiB / max-over-ranks step time.
 
+A plain run (`--gpus 1 --steps K --warmup W`) sets up, warms up, times the K
+steps and prints the result line: metric, value, ms_per_step and the roofline
+figures that the timed region's own HIP events give. `--dump-outputs DIR`
+writes, right after the timed steps, what the last step left in the output
+buffer as float32 DIR/<name>.npy (at N > 1: DIR/rank<r>_<name>.npy): out_head
+and out_tail, the first and last 2^20 elements, and out_sample, 2^22 elements
+at fixed seeded positions. The inputs are seeded, so two builds of the library
+run with the same arguments can be compared file for file.
+
+Everything else runs only with `--full`: the per-launch timing pass, the
+stream ceilings, the host end-to-end leg, the CPU baseline and, at N > 1, the
+collective legs. Without it the roofline's kernel_ms_median / kernel_ms_best
+and ceiling_* / frac_of_* fields and host_e2e are absent, and cpu_baseline and
+collective are null.
+
 Extra JSON fields:
   roofline     — the dominant kernel's algorithmic bytes per launch / its mean
                  launch duration (HIP events on the launch stream) vs the
-                 8 TB/s HBM3E peak; `traffic` = HBM bytes per launch from the
+                 8 TB/s HBM3E peak; (full) kernel_ms_median / kernel_ms_best
+                 from a per-launch pass after the timed region; `traffic` =
+                 HBM bytes per launch from the
                  committed rocprofv3 PMC pass (profiles/pmc_latest.json) — NOT
                  measured in this run: `traffic_provenance` names its box/run;
                  `ceiling_mixed` = the same tile's 8:1 read/write stream with
@@ -959,7 +976,38 @@ def parse_args(argv=None):
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--cpu-seconds", type=float, default=1.5)
     ap.add_argument("--check", action="store_true", help="verify step output against the oracle (sampled)")
-    return ap.parse_args(argv)
+    ap.add_argument("--full", action="store_true",
+                    help="also run everything beside the headline figure: per-launch timings, stream ceilings, "
+                         "the host end-to-end leg, the CPU baseline and, at N > 1, the collective legs")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last step computed as DIR/<name>.npy (float32)")
+    args = ap.parse_args(argv)
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
+    return args
+
+
+# --dump-outputs: the 256 MiB output is written as its first and last
+# DUMP_EDGE elements plus DUMP_SAMPLE elements at fixed seeded positions
+# (24 MiB of float32 in all)
+DUMP_EDGE = 1 << 20
+DUMP_SAMPLE = 1 << 22
+DUMP_SEED = 20240229
+
+
+def dump_outputs(torch, out, directory: str, rank: int, world: int) -> None:
+    """What a caller of the timed path receives from its last step: the
+    output buffer of nbxReduceMulti, as float32 .npy files (module docstring).
+    The inputs are seeded, so two runs with the same arguments write the same
+    arrays unless the library computes something else."""
+    import numpy as np
+    os.makedirs(directory, exist_ok=True)
+    prefix = "" if world == 1 else f"rank{rank}_"
+    idx = np.random.default_rng(DUMP_SEED).integers(0, COUNT, DUMP_SAMPLE, dtype=np.int64)
+    parts = {"out_head": out[:DUMP_EDGE], "out_tail": out[COUNT - DUMP_EDGE:],
+             "out_sample": out[torch.from_numpy(idx).to(out.device)]}
+    for name, t in parts.items():
+        np.save(os.path.join(directory, prefix + name + ".npy"), t.cpu().numpy().astype(np.float32, copy=False))
 
 
 def headline(args, world: int, rank: int, local: int) -> dict:
@@ -1025,13 +1073,15 @@ def headline(args, world: int, rank: int, local: int) -> dict:
         for s in srcs[1:]:
             ref = ref + s[idx]
         assert torch.equal(out[idx], ref), "bench output differs from the left-fold reference"
+    if args.dump_outputs:
+        dump_outputs(torch, out, args.dump_outputs, rank, world)
 
     achieved = ALG_BYTES / (kern_avg_ms * 1e-3) / 1e9
     # median and best per launch too — a separate pass after the
     # timed region, one event pair per launch (the timed region brackets all K
     # launches with one pair: an event between launches costs ~1.5 %)
     per = []
-    for _ in range(max(args.steps, 5)):
+    for _ in range(max(args.steps, 5) if args.full else 0):
         e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
         e0.record(stream)
         step()
@@ -1041,7 +1091,7 @@ def headline(args, world: int, rank: int, local: int) -> dict:
     per_ms = sorted(a.elapsed_time(b) for a, b in per)
     traffic, traffic_src = _pmc_traffic()
     ceil = None
-    if os.environ.get("NBX_BENCH_CEILING", "1") != "0":
+    if args.full and os.environ.get("NBX_BENCH_CEILING", "1") != "0":
         ceil = stream_ceilings(torch, nbx, srcs, out, stream)
     result = {
         "metric": METRIC,
@@ -1068,14 +1118,16 @@ def headline(args, world: int, rank: int, local: int) -> dict:
                      "tile_schedule": "static" if os.environ.get("NBX_DYNAMIC_TILES", "1") == "0"
                      else "dynamic (per-stream tile counter)",
                      "kernel_avg_ms": round(kern_avg_ms, 5),
-                     "kernel_ms_median": round(per_ms[len(per_ms) // 2], 5),
-                     "kernel_ms_best": round(per_ms[0], 5),
-                     "per_launch_what": f"{len(per_ms)} launches after the timed region, one event pair each",
                      "alg_bytes_per_launch": ALG_BYTES},
         "cpu_baseline": None,
         "collective": None,
         "build": _build_stamp(nbx),
     }
+    if per_ms:
+        result["roofline"].update({
+            "kernel_ms_median": round(per_ms[len(per_ms) // 2], 5),
+            "kernel_ms_best": round(per_ms[0], 5),
+            "per_launch_what": f"{len(per_ms)} launches after the timed region, one event pair each"})
     if ceil:
         rf = result["roofline"]
         rf["ceiling_read"], rf["ceiling_write"], rf["ceiling_copy"] = ceil["read_GBs"], ceil["write_GBs"], ceil["copy_GBs"]
@@ -1092,7 +1144,7 @@ def headline(args, world: int, rank: int, local: int) -> dict:
         every = [None] * world
         dist.all_gather_object(every, mine)
         result["per_rank"] = every
-    if world == 1 and os.environ.get("NBX_BENCH_E2E", "1") != "0" and not args.no_cpu_baseline:
+    if args.full and world == 1 and os.environ.get("NBX_BENCH_E2E", "1") != "0" and not args.no_cpu_baseline:
         result["host_e2e"] = host_e2e_leg(torch, nbx, srcs, out, stream, op)
     del srcs, out
     torch.cuda.empty_cache()
@@ -1130,8 +1182,9 @@ def run_legs(result: dict, world: int, rank: int, local: int, child, clique_chil
 def main(argv=None):
     args = parse_args(argv)
     env_world = int(os.environ.get("WORLD_SIZE", "1"))
-    child = _spawn_collective_leg(env_world)
-    clique_child = _spawn_clique_leg(env_world, int(os.environ.get("RANK", "0")))
+    # the N > 1 legs run only with --full
+    child = _spawn_collective_leg(env_world) if args.full else None
+    clique_child = _spawn_clique_leg(env_world, int(os.environ.get("RANK", "0"))) if args.full else None
     import torch
     world, rank, local = _dist_init()
     if args.gpus != world and world > 1:
@@ -1146,7 +1199,7 @@ def main(argv=None):
         wd = Watchdog(budget.total + WATCHDOG_GRACE_S, emitter, [child, clique_child])
         result["collective"] = run_legs(result, world, rank, local, child, clique_child, emitter, budget)
         wd.cancel()
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if args.full and rank == 0 and world == 1 and not args.no_cpu_baseline:
         result["cpu_baseline"] = cpu_baseline(args.cpu_seconds)
     emitter.final(result)
     if world > 1:

@@ -73,7 +73,7 @@ if os.environ.get("STUB_MODE") == "hang":
     def hanging_rccl(world):
         time.sleep(3600)
     bench.rccl_leg = hanging_rccl
-sys.exit(bench.main(["--gpus", "2", "--steps", "1", "--warmup", "0"]))
+sys.exit(bench.main(["--gpus", "2", "--steps", "1", "--warmup", "0", "--full"]))
 '''
 
 

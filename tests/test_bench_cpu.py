@@ -39,3 +39,31 @@ def test_simple_hbm_model():
     assert m8["staging_model_bytes_per_rank"] == 2 * ((1 << 30) + 2 * 7 * (1 << 30) // 8)
     if m8["measured_over_model"] is not None:                 # the committed PMC summary
         assert 0.95 < m8["measured_over_model"]["direct"] < 1.1
+
+
+def test_plain_run_options():
+    a = bench.parse_args(["--gpus", "1", "--steps", "7", "--warmup", "2"])
+    assert (a.steps, a.warmup, a.full, a.dump_outputs) == (7, 2, False, None)
+    a = bench.parse_args(["--full", "--dump-outputs", "d"])
+    assert a.full and a.dump_outputs == "d"
+
+
+def test_dump_outputs_fixed_sample(tmp_path):
+    """--dump-outputs: float32 arrays, under 64 MB in all, the same positions
+    on every call."""
+    import numpy as np
+    import torch
+    out = torch.arange(bench.COUNT, dtype=torch.float32)   # exact below 2^24, monotonic above
+    bench.dump_outputs(torch, out, str(tmp_path / "a"), 0, 1)
+    bench.dump_outputs(torch, out, str(tmp_path / "b"), 1, 2)
+    files = sorted(os.listdir(tmp_path / "a"))
+    assert files == ["out_head.npy", "out_sample.npy", "out_tail.npy"]
+    assert sorted(os.listdir(tmp_path / "b")) == ["rank1_" + f for f in files]
+    arrs = {f: np.load(tmp_path / "a" / f) for f in files}
+    assert all(x.dtype == np.float32 for x in arrs.values())
+    assert sum(x.nbytes for x in arrs.values()) <= 64 * 10**6
+    assert arrs["out_head.npy"][-1] == bench.DUMP_EDGE - 1
+    assert arrs["out_tail.npy"][-1] == out[-1].item()
+    assert arrs["out_sample.npy"].size == bench.DUMP_SAMPLE
+    for f in files:
+        assert np.array_equal(arrs[f], np.load(tmp_path / "b" / ("rank1_" + f)))
