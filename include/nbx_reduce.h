@@ -72,6 +72,46 @@ ncclResult_t nbxReduceMulti(void* const* dsts, int nDsts,
                             nbxDevRedOpFull op, int nPreOpSrcs, int postOp,
                             ncclStream_t stream);
 
+/* fp32-accumulating ("wide") form of the sum, for low-precision sources:
+ * every source is widened once, the fold runs in fp32, and the result is
+ * narrowed once or not at all. This is NOT the reference's rule (which
+ * nbxReduceMulti keeps: the accumulator is rounded to the element type after
+ * every source, so 1.0 + 7 x 2^-9 in bf16 stays 1.0); it is opt-in.
+ *   for every element i in [0, count):
+ *     acc = f32(srcs[0][i]);                 if 0 < nPreOpSrcs: acc = acc * s
+ *     for k = 1 .. nSrcs-1:  v = f32(srcs[k][i]);  if k < nPreOpSrcs: v = v * s;  acc = acc + v
+ *     every dsts[d][i] = (dstType == ncclFloat32) ? acc : narrow(acc)
+ * f32() is exact; every multiply and add is one IEEE fp32 round-to-nearest-even
+ * operation (never fused, denormals kept), folded in source order, so the
+ * result is deterministic. narrow() is the type's narrowing applied once:
+ * RNE for f16 / bf16 (f16 overflow -> inf), RNE behind SATFINITE for fp8
+ * (finite overflow -> +-max finite; inf and NaN as in nbxReduceMulti).
+ * srcType: ncclFloat16, ncclBfloat16, ncclFloat8e4m3, ncclFloat8e5m2.
+ * dstType: srcType, or ncclFloat32 (all destinations share it).
+ * op: nbxDevSum or nbxDevPreMulSum. The PreMulSum scalar s is an FP32 value
+ * whatever srcType is: by value the low 32 bits of scalarArg, or with
+ * scalarArgIsPtr the device address of a float (non-NULL, 4-byte aligned),
+ * read while the kernel runs. nbxHostToDevRedOp(&op, ncclAvg, ncclFloat32, n)
+ * therefore yields the wide average. Prod, MinMax (already exact through
+ * nbxReduceMulti) and SumPostDiv: ncclInvalidArgument.
+ * Limits and errors as nbxReduceMulti, every check before any device call;
+ * count == 0 is a no-op after the type and op checks. Pointers are aligned to
+ * their own element size. A destination of srcType may be one of the sources
+ * (in place); an fp32 destination whose range overlaps any source range is
+ * ncclInvalidArgument. 16-byte packs when the sources share one misalignment
+ * modulo 16 and every destination is 16-byte aligned behind the head elements
+ * that align them (an fp32 destination: (dst + 4 * head) % 16 == 0); any other
+ * layout runs one element per lane — there is no realigning (LDS-DMA) path
+ * here. More than 8 sources fold in ordered passes through an fp32 partial
+ * (dsts[0] for an fp32 output, else stream-ordered scratch of 4 * count
+ * bytes), so the result is still the single fp32 left fold.
+ * Stream-ordered, asynchronous and graph-capturable. */
+ncclResult_t nbxReduceMultiWide(void* const* dsts, int nDsts,
+                                const void* const* srcs, int nSrcs,
+                                size_t count, ncclDataType_t srcType,
+                                ncclDataType_t dstType, nbxDevRedOpFull op,
+                                int nPreOpSrcs, ncclStream_t stream);
+
 /* One bucket of a batched reduction (same meaning as nbxReduceMulti's arguments). */
 typedef struct {
   void* const* dsts;

@@ -164,6 +164,9 @@ _SIGS = {
                            ctypes.c_void_p],
     "nbxReduceMultiBatch": [ctypes.POINTER(ReduceTask), ctypes.c_int, ctypes.c_int, DevRedOpFull, ctypes.c_int,
                             ctypes.c_int, ctypes.c_void_p],
+    "nbxReduceMultiWide": [ctypes.POINTER(ctypes.c_void_p), ctypes.c_int, ctypes.POINTER(ctypes.c_void_p),
+                           ctypes.c_int, ctypes.c_size_t, ctypes.c_int, ctypes.c_int, DevRedOpFull, ctypes.c_int,
+                           ctypes.c_void_p],
     "nbxSetLaunchConfig": [ctypes.c_int, ctypes.c_int],
     "nbxGetLaunchConfig": [ctypes.POINTER(ctypes.c_int), ctypes.POINTER(ctypes.c_int)],
     "nbxKernelCount": [],
@@ -338,6 +341,23 @@ def reduce_multi(dsts: Sequence[int], srcs: Sequence[int], count: int, dtype: in
                  n_pre_op_srcs: int = 0, post_op: bool = False, stream: int = 0) -> None:
     """The hot path: ordered left fold of `srcs` into every `dsts` (reduceCopy semantics)."""
     _check(reduce_multi_raw(dsts, srcs, count, dtype, op, n_pre_op_srcs, post_op, stream), "nbxReduceMulti")
+
+
+def reduce_multi_wide_raw(dsts: Sequence[int], srcs: Sequence[int], count: int, src_type: int, dst_type: int,
+                          op: DevRedOpFull, n_pre_op_srcs: int = 0, stream: int = 0) -> int:
+    """Call nbxReduceMultiWide; returns the ncclResult_t code (no raise)."""
+    d = (ctypes.c_void_p * max(1, len(dsts)))(*[ctypes.c_void_p(int(x)) for x in dsts])
+    s = (ctypes.c_void_p * max(1, len(srcs)))(*[ctypes.c_void_p(int(x)) for x in srcs])
+    return load_library().nbxReduceMultiWide(d, len(dsts), s, len(srcs), int(count), int(src_type), int(dst_type),
+                                             op, int(n_pre_op_srcs), ctypes.c_void_p(int(stream)))
+
+
+def reduce_multi_wide(dsts: Sequence[int], srcs: Sequence[int], count: int, src_type: int, dst_type: int,
+                      op: DevRedOpFull, n_pre_op_srcs: int = 0, stream: int = 0) -> None:
+    """fp32-accumulating sum of f16 / bf16 / fp8 `srcs` into every `dsts` (of `src_type`, or fp32):
+    one rounding at the end instead of one per source. The PreMulSum scalar is an fp32 value."""
+    _check(reduce_multi_wide_raw(dsts, srcs, count, src_type, dst_type, op, n_pre_op_srcs, stream),
+           "nbxReduceMultiWide")
 
 
 def reduce_multi_batch_raw(buckets: Sequence[tuple], dtype: int, op: DevRedOpFull, n_pre_op_srcs: int = 0,

@@ -131,4 +131,18 @@ struct KernelSet {
   int valid;
 };
 
+// Launch table for one source type of the fp32-accumulating sums (nbx_wide.h,
+// nbxReduceMultiWide). One tile shape per source count: 4 packs per lane per
+// source from 4 sources (the per-step kernels' big tile for 5-8), one below
+// (their small tile, which wins for 1-3 sources).
+constexpr int wideUnroll(int nSrcs) { return nSrcs >= 4 ? 4 : 1; }
+
+struct WideSet {
+  const void* packs[2][2][kMaxKSrcs];  // [0 = source-type output, 1 = fp32 output][source 0 is an fp32 partial][nSrcs-1]
+  const void* elts[2][2];              // element kernels, same first two indices
+  int blocksPerCU;                     // at least this many unrolled-tile workgroups per CU
+  int eltBytes;
+  int valid;
+};
+
 }  // namespace nbx

@@ -55,6 +55,19 @@ const KernelTable& table() {
   return g_table;
 }
 
+// fp32-accumulating sums (nbx_wide.h): their own table, so nbxKernelCount and
+// KernelSet stay as they are.
+WideTable g_wide;
+std::once_flag g_wideOnce;
+
+const WideTable& wideTable() {
+  std::call_once(g_wideOnce, [] {
+    std::memset(&g_wide, 0, sizeof(g_wide));
+    fillWide(g_wide);
+  });
+  return g_wide;
+}
+
 // Launch configuration (NCCL_NTHREADS / NCCL_MAX_NCHANNELS analogues).
 std::atomic<int> g_maxBlocksPerCU{0};   // 0 = default per variant
 std::atomic<int> g_variant{0};          // 0 = auto, 1 = force small tile, 2 = force big tile
@@ -167,9 +180,16 @@ size_t peelElts(uintptr_t dst, int eb) {
   return mis ? (size_t)((line - mis) / (unsigned)eb) : 0;
 }
 
-bool overlaps(const void* a, const void* b, size_t bytes) {
+bool overlaps(const void* a, size_t aBytes, const void* b, size_t bBytes) {
   uintptr_t x = (uintptr_t)a, y = (uintptr_t)b;
-  return x < y + bytes && y < x + bytes;
+  return x < y + bBytes && y < x + aBytes;
+}
+bool overlaps(const void* a, const void* b, size_t bytes) { return overlaps(a, bytes, b, bytes); }
+
+// Workgroups of a tiled launch: one per tile up to the cap, at least one.
+size_t cappedGrid(size_t tiles, size_t maxBlocks) {
+  const size_t grid = tiles < maxBlocks ? tiles : maxBlocks;
+  return grid == 0 ? 1 : grid;
 }
 
 // Dynamic tiles (kernels' forEachTile): one 32-bit counter per (device,
@@ -322,8 +342,7 @@ ncclResult_t launchPass(const KernelSet& ks, void* const* dsts, int nDsts, const
       if (need > (size_t)perCU && need <= (size_t)midPerCU) perCU = (int)need;
     }
     const size_t maxBlocks = (size_t)cus * (size_t)perCU;
-    size_t grid = tiles < maxBlocks ? tiles : maxBlocks;
-    if (grid == 0) grid = 1;
+    const size_t grid = cappedGrid(tiles, maxBlocks);
     a.variant = big ? 1 : 0;
     // dynamic tiles for big tiles only: small tiles (1-3 sources, 3-5
     // workgroups per CU, 16x the atomics) collapse to 0.7-1.4 TB/s on the
@@ -694,6 +713,140 @@ ncclResult_t reduceMultiImpl(void* const* dsts, int nDsts, const void* const* sr
     r = launchPass(ks, last ? dsts : partDst, last ? nDsts : 1, ps, n, count, op, m, last ? post : 0, acq, st);
   }
   if (alias && hipFreeAsync(part, st) != hipSuccess && r == ncclSuccess) r = ncclUnhandledCudaError;
+  return r;
+}
+
+// One pass of the fp32-accumulating kernels (nbx_wide.h) over <= kMaxKSrcs
+// sources. partFirst: srcs[0] is the fp32 partial of the earlier passes.
+// fast / head are decided once per call from the caller's pointers (every
+// pass of a call folds sources of the same alignment into the same partial).
+ncclResult_t launchWidePass(const WideSet& ws, bool out32, bool partFirst, bool fast, size_t head, void* const* dsts,
+                            int nDsts, const void* const* srcs, int nSrcs, size_t count, const nbxDevRedOpFull& op,
+                            uint32_t preMask, hipStream_t stream) {
+  KArgs a;
+  std::memset(&a, 0, sizeof(a));
+  for (int s = 0; s < nSrcs; s++) a.src[s] = srcs[s];
+  for (int d = 0; d < kMaxKDsts; d++) a.dst[d] = dsts[d < nDsts ? d : 0];
+  a.nElts = count;
+  if (op.op == nbxDevPreMulSum) {   // an fp32 scalar: the low 32 bits, or a device float
+    a.arg = op.scalarArgIsPtr ? 0 : (op.scalarArg & 0xffffffffull);
+    a.argPtr = op.scalarArgIsPtr ? (const void*)(uintptr_t)op.scalarArg : nullptr;
+  }
+  a.preMask = preMask;
+  a.nSrcs = nSrcs;
+  a.nDsts = nDsts;
+  const int dev = launchDevice(stream);
+  const size_t cus = (size_t)cuCount(dev);
+  void* args[] = {&a};
+  hipError_t err;
+  if (fast) {
+    const size_t nPacks = (count - head) / (size_t)(16 / ws.eltBytes);
+    a.headElts = (int)head;
+    a.nPacks = nPacks;
+    const int unroll = wideUnroll(nSrcs);
+    const bool big = unroll > 1;
+    const size_t tile = (size_t)unroll * kBlock;
+    const size_t tiles = (nPacks + tile - 1) / tile;
+    int perCU = maxBlocksPerCU(big, nSrcs * unroll);
+    static const bool envPerCU = envInt("NBX_BLOCKS_PER_CU", 0) > 0;
+    if (big && !envPerCU && g_maxBlocksPerCU.load(std::memory_order_relaxed) == 0 && perCU < ws.blocksPerCU)
+      perCU = ws.blocksPerCU;
+    const size_t grid = cappedGrid(tiles, cus * (size_t)perCU);
+    a.variant = big ? 1 : 0;
+    // dynamic tiles under launchPass's rule: unrolled tiles, long launches
+    DynLaunch dyn;
+    if (big && tiles >= (size_t)dynMinTilesPerWG() * grid) dyn.begin(dev, stream, tiles, a);
+    err = hipLaunchKernel(ws.packs[out32 ? 1 : 0][partFirst ? 1 : 0][nSrcs - 1], dim3((unsigned)grid), dim3(kBlock),
+                          args, 0, stream);
+    dyn.done(err == hipSuccess);
+  } else {
+    const size_t blocks = (count + kBlock - 1) / kBlock;
+    const size_t grid = cappedGrid(blocks, cus * (size_t)maxBlocksPerCU(false, nSrcs, /*classic=*/true));
+    err = hipLaunchKernel(ws.elts[out32 ? 1 : 0][partFirst ? 1 : 0], dim3((unsigned)grid), dim3(kBlock), args, 0,
+                          stream);
+  }
+  if (err != hipSuccess) {
+    std::fprintf(stderr, "nbx: wide kernel launch failed: %s\n", hipGetErrorString(err));
+    return ncclUnhandledCudaError;
+  }
+  return ncclSuccess;
+}
+
+ncclResult_t reduceMultiWideImpl(void* const* dsts, int nDsts, const void* const* srcs, int nSrcs, size_t count,
+                                 ncclDataType_t srcType, ncclDataType_t dstType, nbxDevRedOpFull op, int nPreOpSrcs,
+                                 ncclStream_t stream) {
+  if (nSrcs < 1 || nSrcs > NBX_MAX_SRCS || nDsts < 1 || nDsts > NBX_MAX_DSTS) return ncclInvalidArgument;
+  if (srcs == nullptr || dsts == nullptr) return ncclInvalidArgument;
+  const int st = (int)srcType, dt = (int)dstType;
+  if (st < 0 || st >= kNumTypes || !wideTable()[st].valid) return ncclInvalidArgument;   // f16, bf16, fp8 only
+  if (dt != st && dt != (int)ncclFloat32) return ncclInvalidArgument;
+  if (op.op != nbxDevSum && op.op != nbxDevPreMulSum) return ncclInvalidArgument;
+  const bool pre = op.op == nbxDevPreMulSum;
+  if (pre && op.scalarArgIsPtr && (op.scalarArg == 0 || (op.scalarArg & 3u) != 0)) return ncclInvalidArgument;
+  if (count == 0) return ncclSuccess;
+  const WideSet& ws = wideTable()[st];
+  const bool out32 = dt != st;
+  const size_t eb = (size_t)ws.eltBytes, deb = out32 ? sizeof(float) : eb;
+  for (int s = 0; s < nSrcs; s++)
+    if (srcs[s] == nullptr || ((uintptr_t)srcs[s] % eb) != 0) return ncclInvalidArgument;
+  for (int d = 0; d < nDsts; d++)
+    if (dsts[d] == nullptr || ((uintptr_t)dsts[d] % deb) != 0) return ncclInvalidArgument;
+  // a source-type destination may be a source (in place); an fp32 one may
+  // not touch any source: its elements are wider than the ones still to be read
+  if (out32)
+    for (int d = 0; d < nDsts; d++)
+      for (int s = 0; s < nSrcs; s++)
+        if (overlaps(dsts[d], count * deb, srcs[s], count * eb)) return ncclInvalidArgument;
+  if (nPreOpSrcs < 0) nPreOpSrcs = 0;
+  hipStream_t strm = (hipStream_t)stream;
+
+  // pack kernel: the sources share one misalignment modulo 16, and behind the
+  // head elements that align them every destination is 16-byte aligned
+  const unsigned mis = (unsigned)((uintptr_t)srcs[0] & 15u);
+  size_t head = mis ? (size_t)(16u - mis) / eb : 0;
+  bool fast = true;
+  for (int s = 1; s < nSrcs; s++) fast &= (((uintptr_t)srcs[s] & 15u) == mis);
+  for (int d = 0; d < nDsts; d++) fast &= ((((uintptr_t)dsts[d] + head * deb) & 15u) == 0);
+  if (head > count) head = count;
+
+  auto maskFor = [&](int first, int n, int slot0) {   // sources [first, first + n) sit in slots slot0 ...
+    uint32_t m = 0;
+    if (pre)
+      for (int k = 0; k < n; k++)
+        if (first + k < nPreOpSrcs) m |= 1u << (slot0 + k);
+    return m;
+  };
+  if (nSrcs <= kMaxKSrcs)
+    return launchWidePass(ws, out32, false, fast, head, dsts, nDsts, srcs, nSrcs, count, op, maskFor(0, nSrcs, 0),
+                          strm);
+
+  // > 8 sources: ordered passes of 8 + 7 + 7 ... through an fp32 partial that
+  // is never narrowed, so the result is the single fp32 left fold. The
+  // partial lives in dsts[0] when the output is fp32 (no source overlaps it),
+  // else in stream-ordered scratch (graph-capturable), placed so that its
+  // body behind the head elements is 16-byte aligned like the sources'.
+  void* scratch = nullptr;
+  void* part = dsts[0];
+  if (!out32) {
+    if (hipMallocAsync(&scratch, count * sizeof(float) + 16, strm) != hipSuccess) return ncclUnhandledCudaError;
+    part = (char*)scratch + ((16u - (unsigned)((head * sizeof(float)) & 15u)) & 15u);
+  }
+  void* partDst[1] = {part};
+  // the partial is fp32 whatever the output: its passes use the fp32-output kernels
+  ncclResult_t r = launchWidePass(ws, true, false, fast, head, partDst, 1, srcs, kMaxKSrcs, count, op,
+                                  maskFor(0, kMaxKSrcs, 0), strm);
+  int next = kMaxKSrcs;
+  while (r == ncclSuccess && next < nSrcs) {
+    const void* ps[kMaxKSrcs];
+    ps[0] = part;
+    const int first = next;
+    int n = 1;
+    while (n < kMaxKSrcs && next < nSrcs) ps[n++] = srcs[next++];
+    const bool last = next >= nSrcs;
+    r = launchWidePass(ws, last ? out32 : true, true, fast, head, last ? dsts : partDst, last ? nDsts : 1, ps, n, count,
+                       op, maskFor(first, n - 1, 1), strm);
+  }
+  if (scratch != nullptr && hipFreeAsync(scratch, strm) != hipSuccess && r == ncclSuccess) r = ncclUnhandledCudaError;
   return r;
 }
 
@@ -1129,6 +1282,14 @@ __attribute__((visibility("default"))) ncclResult_t nbxReduceMultiBatch(const nb
                                                                          int nPreOpSrcs, int postOp,
                                                                          ncclStream_t stream) {
   return reduceMultiBatchImpl(tasks, nTasks, datatype, op, nPreOpSrcs, postOp, stream, 0);
+}
+
+__attribute__((visibility("default"))) ncclResult_t nbxReduceMultiWide(void* const* dsts, int nDsts,
+                                                                        const void* const* srcs, int nSrcs,
+                                                                        size_t count, ncclDataType_t srcType,
+                                                                        ncclDataType_t dstType, nbxDevRedOpFull op,
+                                                                        int nPreOpSrcs, ncclStream_t stream) {
+  return reduceMultiWideImpl(dsts, nDsts, srcs, nSrcs, count, srcType, dstType, op, nPreOpSrcs, stream);
 }
 
 __attribute__((visibility("default"))) ncclResult_t nbxSetLaunchConfig(int blocksPerCU, int variant) {

@@ -21,4 +21,8 @@ void fillBF16(KernelTable& t);
 void fillF32(KernelTable& t);
 void fillF64(KernelTable& t);
 void fillFp8(KernelTable& t);
+
+// fp32-accumulating sums: one WideSet per source type (f16, bf16, fp8)
+typedef WideSet WideTable[kNumTypes];
+void fillWide(WideTable& t);
 }  // namespace nbx
