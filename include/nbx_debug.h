@@ -148,6 +148,23 @@ int nbxDebugDynStreamSlots(int device, int which);
 int nbxDebugHoldStream(ncclStream_t stream, int timeoutMs);
 int nbxDebugReleaseStream(int hold);
 
+/* Launch record of the reduction core (test hook): every kernel pass that
+ * nbxReduceMulti / nbxReduceMultiWide launch from the calling thread appends
+ * {family, nSrcs, unroll, flags} to a thread-local log, so a test can see
+ * which kernel a call took. family: 1 small-tile packs, 2 big-tile packs,
+ * 3 elements, 4 realigning LDS-DMA (one kernel per source count), 5 realigning
+ * run-time source count, 6 wide packs, 7 wide elements. nSrcs: the pass's
+ * sources (a later pass of a > 8-source call counts its partial). unroll:
+ * packs per lane per source and tile (1 for the element kernels). flags:
+ * bit 0 dynamic tile schedule, bit 1 fp32 output (wide), bit 2 the first
+ * source is the fp32 partial of earlier passes (wide). Plain host stores; the
+ * log keeps the newest 64 passes.
+ * nbxDebugLaunchLog returns the number of passes since the last
+ * nbxDebugLaunchLogReset() and copies the newest min(maxRecords, 64, that
+ * number) of them, oldest first, four int32 each, to `out`. */
+int nbxDebugLaunchLog(int32_t* out, int maxRecords);
+void nbxDebugLaunchLogReset(void);
+
 #ifdef __cplusplus
 }
 #endif

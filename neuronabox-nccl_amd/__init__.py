@@ -215,6 +215,11 @@ def load_library(path: Optional[str] = None) -> ctypes.CDLL:
         fn.restype = ctypes.c_char_p
     lib.ncclGetErrorString.argtypes = [ctypes.c_int]
     lib.ncclGetLastError.argtypes = [ctypes.c_void_p]
+    # test hook (include/nbx_debug.h): the launch record
+    lib.nbxDebugLaunchLog.argtypes = [ctypes.POINTER(ctypes.c_int32), ctypes.c_int]
+    lib.nbxDebugLaunchLog.restype = ctypes.c_int
+    lib.nbxDebugLaunchLogReset.argtypes = []
+    lib.nbxDebugLaunchLogReset.restype = None
     if path is None:
         _lib = lib
     return lib
@@ -326,6 +331,34 @@ def get_launch_config() -> tuple:
     b, p = ctypes.c_int(), ctypes.c_int()
     _check(load_library().nbxGetLaunchConfig(ctypes.byref(b), ctypes.byref(p)), "nbxGetLaunchConfig")
     return b.value, p.value
+
+
+class LaunchFamily(enum.IntEnum):        # include/nbx_debug.h nbxDebugLaunchLog
+    SmallPacks = 1
+    BigPacks = 2
+    Elements = 3
+    RealignLds = 4
+    RealignRuntime = 5
+    WidePacks = 6
+    WideElements = 7
+
+
+LAUNCH_DYNAMIC, LAUNCH_OUT32, LAUNCH_PART_FIRST = 1, 2, 4
+LAUNCH_LOG_CAP = 64
+
+
+def launch_log_reset() -> None:
+    """Empties the calling thread's launch record (nbxDebugLaunchLogReset)."""
+    load_library().nbxDebugLaunchLogReset()
+
+
+def launch_log(max_records: int = LAUNCH_LOG_CAP) -> tuple:
+    """(passes since the last reset, [(family, nSrcs, unroll, flags), ...] of the newest of them,
+    oldest first) for the calling thread: which kernels its nbxReduceMulti / nbxReduceMultiWide calls took."""
+    buf = (ctypes.c_int32 * (4 * max(1, max_records)))()
+    total = load_library().nbxDebugLaunchLog(buf, int(max_records))
+    k = min(total, max_records, LAUNCH_LOG_CAP)
+    return total, [tuple(buf[4 * i:4 * i + 4]) for i in range(k)]
 
 
 def reduce_multi_raw(dsts: Sequence[int], srcs: Sequence[int], count: int, dtype: int, op: DevRedOpFull,

@@ -283,6 +283,29 @@ uint32_t* shiftDynCounters(int dev, hipStream_t st) {
   return b;
 }
 
+// Launch record (include/nbx_debug.h nbxDebugLaunchLog): the newest
+// kLaunchLogCap passes launched from this thread, as {family, nSrcs, unroll,
+// flags}. Host stores only; nothing reads it but the test hook.
+constexpr int kLaunchLogCap = 64;
+enum LaunchFamily {
+  kFamSmallPacks = 1, kFamBigPacks = 2, kFamElts = 3, kFamShiftedLds = 4, kFamShifted = 5, kFamWidePacks = 6,
+  kFamWideElts = 7
+};
+enum LaunchFlag { kLaunchDynamic = 1, kLaunchOut32 = 2, kLaunchPartFirst = 4 };
+struct LaunchLog {
+  int32_t rec[kLaunchLogCap][4];
+  uint64_t n;
+};
+thread_local LaunchLog t_launchLog;
+
+inline void logLaunch(int family, int nSrcs, int unroll, int flags) {
+  int32_t* r = t_launchLog.rec[t_launchLog.n++ % kLaunchLogCap];
+  r[0] = family;
+  r[1] = nSrcs;
+  r[2] = unroll;
+  r[3] = flags;
+}
+
 // One kernel pass over <= kMaxKSrcs sources.
 ncclResult_t launchPass(const KernelSet& ks, void* const* dsts, int nDsts, const void* const* srcs,
                         int nSrcs, size_t count, const nbxDevRedOpFull& op, uint32_t preMask,
@@ -361,6 +384,8 @@ ncclResult_t launchPass(const KernelSet& ks, void* const* dsts, int nDsts, const
     if (big && tiles >= (size_t)dynMinTilesPerWG() * grid) dyn.begin(dev, stream, tiles, a);
     err = hipLaunchKernel((const void*)ks.packs[big ? 1 : 0][nSrcs - 1], dim3((unsigned)grid), dim3(kBlock), args,
                           0, stream);
+    logLaunch(big ? kFamBigPacks : kFamSmallPacks, nSrcs, big ? ks.unroll[nSrcs - 1] : 1,
+              a.dynCtr != nullptr ? kLaunchDynamic : 0);
     dyn.done(err == hipSuccess);
   } else {
     const unsigned dmis = (unsigned)((uintptr_t)dsts[0] & 15u);
@@ -396,13 +421,17 @@ ncclResult_t launchPass(const KernelSet& ks, void* const* dsts, int nDsts, const
       // 8x the fetches per byte) lost 28 % to the counters' contention, so
       // they stay static (profiles/r2/realign_probe_r4q.jsonl)
       if (fn && nSrcs >= 3 && blocks >= (size_t)dynMinTilesPerWG() * grid) a.dynCtr = shiftDynCounters(dev, stream);
+      const bool perCount = fn != nullptr;
       if (!fn) fn = ks.shifted;
       err = hipLaunchKernel(fn, dim3((unsigned)grid), dim3(threads), args, 0, stream);
+      logLaunch(perCount ? kFamShiftedLds : kFamShifted, nSrcs, perCount ? shiftLdsUnroll(nSrcs) : 1,
+                a.dynCtr != nullptr ? kLaunchDynamic : 0);
     } else {
       size_t blocks = (count + kBlock - 1) / kBlock;
       size_t maxBlocks = (size_t)cus * (size_t)maxBlocksPerCU(false, nSrcs, /*classic=*/true);
       size_t grid = blocks < maxBlocks ? blocks : maxBlocks;
       err = hipLaunchKernel((const void*)ks.elts, dim3((unsigned)grid), dim3(kBlock), args, 0, stream);
+      logLaunch(kFamElts, nSrcs, 1, 0);
     }
   }
   if (err != hipSuccess) {
@@ -739,6 +768,7 @@ ncclResult_t launchWidePass(const WideSet& ws, bool out32, bool partFirst, bool 
   const size_t cus = (size_t)cuCount(dev);
   void* args[] = {&a};
   hipError_t err;
+  const int wideFlags = (out32 ? kLaunchOut32 : 0) | (partFirst ? kLaunchPartFirst : 0);
   if (fast) {
     const size_t nPacks = (count - head) / (size_t)(16 / ws.eltBytes);
     a.headElts = (int)head;
@@ -758,12 +788,14 @@ ncclResult_t launchWidePass(const WideSet& ws, bool out32, bool partFirst, bool 
     if (big && tiles >= (size_t)dynMinTilesPerWG() * grid) dyn.begin(dev, stream, tiles, a);
     err = hipLaunchKernel(ws.packs[out32 ? 1 : 0][partFirst ? 1 : 0][nSrcs - 1], dim3((unsigned)grid), dim3(kBlock),
                           args, 0, stream);
+    logLaunch(kFamWidePacks, nSrcs, unroll, wideFlags | (a.dynCtr != nullptr ? kLaunchDynamic : 0));
     dyn.done(err == hipSuccess);
   } else {
     const size_t blocks = (count + kBlock - 1) / kBlock;
     const size_t grid = cappedGrid(blocks, cus * (size_t)maxBlocksPerCU(false, nSrcs, /*classic=*/true));
     err = hipLaunchKernel(ws.elts[out32 ? 1 : 0][partFirst ? 1 : 0], dim3((unsigned)grid), dim3(kBlock), args, 0,
                           stream);
+    logLaunch(kFamWideElts, nSrcs, 1, wideFlags);
   }
   if (err != hipSuccess) {
     std::fprintf(stderr, "nbx: wide kernel launch failed: %s\n", hipGetErrorString(err));
@@ -1335,6 +1367,19 @@ __attribute__((visibility("default"))) int nbxDebugDynStreamSlots(int device, in
   std::lock_guard<std::mutex> lk(g_shiftDyn[device].mu);
   return g_shiftDyn[device].used;
 }
+
+__attribute__((visibility("default"))) int nbxDebugLaunchLog(int32_t* out, int maxRecords) {
+  const LaunchLog& L = t_launchLog;
+  const uint64_t total = L.n;
+  uint64_t k = total < (uint64_t)kLaunchLogCap ? total : (uint64_t)kLaunchLogCap;
+  if (out == nullptr || maxRecords <= 0) k = 0;
+  else if ((uint64_t)maxRecords < k) k = (uint64_t)maxRecords;
+  for (uint64_t i = 0; i < k; i++)
+    std::memcpy(out + 4 * i, L.rec[(total - k + i) % kLaunchLogCap], sizeof(L.rec[0]));
+  return total > 0x7fffffffull ? 0x7fffffff : (int)total;
+}
+
+__attribute__((visibility("default"))) void nbxDebugLaunchLogReset(void) { t_launchLog.n = 0; }
 
 __attribute__((visibility("default"))) int nbxDebugSetDynMinTiles(int tilesPerWorkgroup) {
   const int prev = dynMinTilesPerWG();
