@@ -148,17 +148,37 @@ int nbxDebugDynStreamSlots(int device, int which);
 int nbxDebugHoldStream(ncclStream_t stream, int timeoutMs);
 int nbxDebugReleaseStream(int hold);
 
-/* Launch record of the reduction core (test hook): every kernel pass that
- * nbxReduceMulti / nbxReduceMultiWide launch from the calling thread appends
+/* Launch record (test hook): every kernel pass that nbxReduceMulti /
+ * nbxReduceMultiWide launch from the calling thread, and every collective
+ * kernel a multi-rank communicator launches from it, appends
  * {family, nSrcs, unroll, flags} to a thread-local log, so a test can see
- * which kernel a call took. family: 1 small-tile packs, 2 big-tile packs,
+ * which kernel a call took.
+ * Reduction core — family: 1 small-tile packs, 2 big-tile packs,
  * 3 elements, 4 realigning LDS-DMA (one kernel per source count), 5 realigning
  * run-time source count, 6 wide packs, 7 wide elements. nSrcs: the pass's
  * sources (a later pass of a > 8-source call counts its partial). unroll:
  * packs per lane per source and tile (1 for the element kernels). flags:
  * bit 0 dynamic tile schedule, bit 1 fp32 output (wide), bit 2 the first
- * source is the fp32 partial of earlier passes (wide). Plain host stores; the
- * log keeps the newest 64 passes.
+ * source is the fp32 partial of earlier passes (wide).
+ * Collective launches of a multi-rank communicator (comm_mp_launch.cc
+ * mpLaunchLL / mpLaunchSimple), one record per kernel launched — family:
+ * 8 LL (kLLColl), 9 LL128 one-shot (kLL128Coll), 10 LL128 two-shot
+ * (kLL128AllReduce2), 11 Simple direct (kSimpleColl; the transport-only call
+ * of nbxDebugTransportAllReduce too), 12 Simple ring (kSimpleRing). nSrcs:
+ * the communicator's rank count. unroll: 1 for LL / LL128; 0 for Simple,
+ * whose kernel picks its fold's unroll on the device from the sources of each
+ * fold (16 for <= 2, 8 for <= 4, else 4: nbx_simple.h simpleFold), which the
+ * host does not know. flags: bit 0 the checking instantiation (LL family:
+ * plan checks, NBX_CHECK_PLANS / NCCL_CHECK_POINTERS; Simple: slice
+ * checksums, NBX_CHECK_SLICES), bits 8.. the segments of a group's calls run
+ * as one launch (0: a single call). A call is recorded on the thread that
+ * launches it, after the launch succeeded: the caller's thread for
+ * ncclAllReduce / ncclReduceScatter / ncclReduce outside a group, the thread
+ * of the outermost ncclGroupEnd for grouped calls. The LL128 self-test of
+ * communicator creation launches collectives too: on the creating thread, or
+ * on the background thread of a non-blocking ncclCommInitRankConfig — reset
+ * the log after creation.
+ * Plain host stores; the log keeps the newest 64 passes.
  * nbxDebugLaunchLog returns the number of passes since the last
  * nbxDebugLaunchLogReset() and copies the newest min(maxRecords, 64, that
  * number) of them, oldest first, four int32 each, to `out`. */

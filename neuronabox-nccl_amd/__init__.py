@@ -341,9 +341,15 @@ class LaunchFamily(enum.IntEnum):        # include/nbx_debug.h nbxDebugLaunchLog
     RealignRuntime = 5
     WidePacks = 6
     WideElements = 7
+    LL = 8                # collective launches of a multi-rank communicator
+    LL128 = 9
+    LL128TwoShot = 10
+    SimpleDirect = 11
+    SimpleRing = 12
 
 
 LAUNCH_DYNAMIC, LAUNCH_OUT32, LAUNCH_PART_FIRST = 1, 2, 4
+LAUNCH_CHECKED, LAUNCH_SEGS_SHIFT = 1, 8   # collective families: checking instantiation, group segments
 LAUNCH_LOG_CAP = 64
 
 
@@ -354,7 +360,8 @@ def launch_log_reset() -> None:
 
 def launch_log(max_records: int = LAUNCH_LOG_CAP) -> tuple:
     """(passes since the last reset, [(family, nSrcs, unroll, flags), ...] of the newest of them,
-    oldest first) for the calling thread: which kernels its nbxReduceMulti / nbxReduceMultiWide calls took."""
+    oldest first) for the calling thread: which kernels its nbxReduceMulti / nbxReduceMultiWide calls and its
+    multi-rank collectives took."""
     buf = (ctypes.c_int32 * (4 * max(1, max_records)))()
     total = load_library().nbxDebugLaunchLog(buf, int(max_records))
     k = min(total, max_records, LAUNCH_LOG_CAP)

@@ -66,6 +66,14 @@ ncclResult_t mpLaunchLL(ncclComm* comm, const MpCall& c, MpProto proto, const Mp
   la.root = c.root;
   la.order = mpOrderArgs(mp);
   la.gridCap = proto == kMpLL ? mp->llGridCap : mp->l128GridCap;
+  // launch record (nbx_debug.h): the kernel family, the checking instantiation
+  // (planSig != 0 picks it in nbx_reduce.cc), the group's segments
+  auto launched = [&](ncclResult_t r, int family) {
+    if (r == ncclSuccess)
+      nbx::logCollLaunch(family, n, 1, (la.planSig != 0 ? nbx::kLaunchChecked : 0) |
+                                           ((int)la.nSegs << nbx::kLaunchSegsShift));
+    return r;
+  };
   // a group's calls as one launch (runMpLLGroup): their slots concatenated, in
   // units of 8-byte packs (LL) or 48-byte lines (LL128 one-shot)
   const uint64_t unit = proto == kMpLL ? 8 : (uint64_t)nbx::kL128DataBytesHost;
@@ -91,15 +99,15 @@ ncclResult_t mpLaunchLL(ncclComm* comm, const MpCall& c, MpProto proto, const Mp
       const uint64_t blockLines =
           ((uint64_t)per * (uint64_t)eb + nbx::kL128DataBytesHost - 1) / nbx::kL128DataBytesHost;
       la.planSig = mp->checkPlans ? nbx::llPlanSig(la, (int32_t)proto, (int32_t)c.dt, c.op.op) : 0;
-      return nbx::launchLL128AllReduce2(c.dt, c.op, la, blockLines, c.stream);
+      return launched(nbx::launchLL128AllReduce2(c.dt, c.op, la, blockLines, c.stream), nbx::kFamLL128x2);
     }
     la.nLines = nSegs > 1 ? units : (slotBytes + nbx::kL128DataBytesHost - 1) / nbx::kL128DataBytesHost;
     la.planSig = mp->checkPlans ? nbx::llPlanSig(la, (int32_t)proto, (int32_t)c.dt, c.op.op) : 0;
-    return nbx::launchLL128Coll(c.dt, c.op, la, c.stream);
+    return launched(nbx::launchLL128Coll(c.dt, c.op, la, c.stream), nbx::kFamLL128);
   }
   if (nSegs > 1) la.nPacks = units;
   la.planSig = mp->checkPlans ? nbx::llPlanSig(la, (int32_t)proto, (int32_t)c.dt, c.op.op) : 0;
-  return nbx::launchLLColl(c.dt, c.op, la, c.stream);
+  return launched(nbx::launchLLColl(c.dt, c.op, la, c.stream), nbx::kFamLL);
 }
 
 // Simple protocol: one kernel (nbx_simple.h). Blocks: AllReduce / Reduce the
@@ -184,7 +192,12 @@ ncclResult_t mpLaunchSimple(ncclComm* comm, const MpCall* calls, int nc, bool tr
   sa.planSig = mp->checkPlans ? nbx::simplePlanSig(sa, (uint32_t)grid, (int32_t)c.dt, c.op.op) : 0;
   sa.checkSlices = mp->checkSlices ? (mp->sliceFaultRank == me ? 2 : 1) : 0;   // 2: test hook, a wrong stamp
   sa.order = mpOrderArgs(mp);
-  return nbx::launchSimple(c.dt, c.op, sa, (unsigned)grid, mp->ring && !transport, c.stream);
+  const bool ring = mp->ring && !transport;
+  NCCLCHECK(nbx::launchSimple(c.dt, c.op, sa, (unsigned)grid, ring, c.stream));
+  // launch record (nbx_debug.h): unroll 0, the kernel picks it from its source count
+  nbx::logCollLaunch(ring ? nbx::kFamSimpleRing : nbx::kFamSimple, n, 0,
+                     (sa.checkSlices ? nbx::kLaunchChecked : 0) | ((int)sa.nSegs << nbx::kLaunchSegsShift));
+  return ncclSuccess;
 }
 
 ncclResult_t runMpColl(ncclComm* comm, const MpCall& c0) {

@@ -63,4 +63,9 @@ ncclResult_t launchLinkProbe(char* const* peerStageDev, int me, int n, uint64_t 
 // LL128 two-shot AllReduce (args.nLines = sub-slot lines; blockLines sizes the grid).
 ncclResult_t launchLL128AllReduce2(ncclDataType_t dt, const nbxDevRedOpFull& op, LLArgs& args, uint64_t blockLines,
                                    hipStream_t stream);
+// Launch record of the collective launches (include/nbx_debug.h
+// nbxDebugLaunchLog, families 8-12): one entry in the calling thread's log.
+constexpr int kFamLL = 8, kFamLL128 = 9, kFamLL128x2 = 10, kFamSimple = 11, kFamSimpleRing = 12;
+constexpr int kLaunchChecked = 1, kLaunchSegsShift = 8;
+void logCollLaunch(int family, int nRanks, int unroll, int flags);
 }  // namespace nbx

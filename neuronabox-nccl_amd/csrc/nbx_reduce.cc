@@ -285,7 +285,9 @@ uint32_t* shiftDynCounters(int dev, hipStream_t st) {
 
 // Launch record (include/nbx_debug.h nbxDebugLaunchLog): the newest
 // kLaunchLogCap passes launched from this thread, as {family, nSrcs, unroll,
-// flags}. Host stores only; nothing reads it but the test hook.
+// flags}. Host stores only; nothing reads it but the test hook. The
+// collective launches (comm_mp_launch.cc, families 8-12 in nbx_internal.h)
+// append to the same log through nbx::logCollLaunch.
 constexpr int kLaunchLogCap = 64;
 enum LaunchFamily {
   kFamSmallPacks = 1, kFamBigPacks = 2, kFamElts = 3, kFamShiftedLds = 4, kFamShifted = 5, kFamWidePacks = 6,
@@ -488,6 +490,8 @@ void DynLaunch::done(bool launched) {
 }  // namespace nbx
 
 namespace nbx {
+void logCollLaunch(int family, int nRanks, int unroll, int flags) { logLaunch(family, nRanks, unroll, flags); }
+
 // Workgroup cap of the LL-family kernels from an env knob, clamped to [1, 1024].
 size_t gridCapFromEnv(const char* name, long dflt) {
   const char* v = std::getenv(name);
