@@ -149,8 +149,8 @@ int nbxDebugHoldStream(ncclStream_t stream, int timeoutMs);
 int nbxDebugReleaseStream(int hold);
 
 /* Launch record (test hook): every kernel pass that nbxReduceMulti /
- * nbxReduceMultiWide launch from the calling thread, and every collective
- * kernel a multi-rank communicator launches from it, appends
+ * nbxReduceMultiWide / nbxReduceMultiBatch launch from the calling thread, and
+ * every collective kernel a multi-rank communicator launches from it, appends
  * {family, nSrcs, unroll, flags} to a thread-local log, so a test can see
  * which kernel a call took.
  * Reduction core — family: 1 small-tile packs, 2 big-tile packs,
@@ -178,6 +178,18 @@ int nbxDebugReleaseStream(int hold);
  * communicator creation launches collectives too: on the creating thread, or
  * on the background thread of a non-blocking ncclCommInitRankConfig — reset
  * the log after creation.
+ * Batched launches of nbxReduceMultiBatch (nbx_reduce.cc BatchPacker::flush /
+ * launchBatchList), one record per kernel launched, after the launch
+ * succeeded — family: 13 kernel-argument batch (kReduceBatch), 14 work-list
+ * batch (kReduceBatchList). nSrcs: the launch's source count. unroll: 1.
+ * flags: bit 0 unused, bits 8.. the buckets of that launch (buckets of count
+ * 0 are never in a launch and are not counted). Buckets that do not go into
+ * a batch (mixed alignment, > 8 sources, 4+ sources filling the GPU alone,
+ * launch variant 2) leave the records of the single-bucket path, families
+ * 1-5. Order of one call's records: those single buckets first, in bucket
+ * order; then, per source count ascending, that count's work-list launches
+ * followed by its kernel-argument launches (the buckets no free table slot
+ * was left for; all of them with work lists off or for a small set).
  * Plain host stores; the log keeps the newest 64 passes.
  * nbxDebugLaunchLog returns the number of passes since the last
  * nbxDebugLaunchLogReset() and copies the newest min(maxRecords, 64, that

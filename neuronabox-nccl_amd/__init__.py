@@ -346,10 +346,12 @@ class LaunchFamily(enum.IntEnum):        # include/nbx_debug.h nbxDebugLaunchLog
     LL128TwoShot = 10
     SimpleDirect = 11
     SimpleRing = 12
+    BatchKernarg = 13     # nbxReduceMultiBatch launches: flags bits 8.. = buckets of the launch
+    BatchList = 14
 
 
 LAUNCH_DYNAMIC, LAUNCH_OUT32, LAUNCH_PART_FIRST = 1, 2, 4
-LAUNCH_CHECKED, LAUNCH_SEGS_SHIFT = 1, 8   # collective families: checking instantiation, group segments
+LAUNCH_CHECKED, LAUNCH_SEGS_SHIFT = 1, 8   # collective families: checking instantiation, group segments (batch: buckets)
 LAUNCH_LOG_CAP = 64
 
 
@@ -360,8 +362,8 @@ def launch_log_reset() -> None:
 
 def launch_log(max_records: int = LAUNCH_LOG_CAP) -> tuple:
     """(passes since the last reset, [(family, nSrcs, unroll, flags), ...] of the newest of them,
-    oldest first) for the calling thread: which kernels its nbxReduceMulti / nbxReduceMultiWide calls and its
-    multi-rank collectives took."""
+    oldest first) for the calling thread: which kernels its nbxReduceMulti / nbxReduceMultiWide /
+    nbxReduceMultiBatch calls and its multi-rank collectives took."""
     buf = (ctypes.c_int32 * (4 * max(1, max_records)))()
     total = load_library().nbxDebugLaunchLog(buf, int(max_records))
     k = min(total, max_records, LAUNCH_LOG_CAP)

@@ -291,7 +291,8 @@ uint32_t* shiftDynCounters(int dev, hipStream_t st) {
 constexpr int kLaunchLogCap = 64;
 enum LaunchFamily {
   kFamSmallPacks = 1, kFamBigPacks = 2, kFamElts = 3, kFamShiftedLds = 4, kFamShifted = 5, kFamWidePacks = 6,
-  kFamWideElts = 7
+  kFamWideElts = 7,
+  kFamBatch = 13, kFamBatchList = 14   // batched buckets: flags bits kLaunchSegsShift.. = buckets of the launch
 };
 enum LaunchFlag { kLaunchDynamic = 1, kLaunchOut32 = 2, kLaunchPartFirst = 4 };
 struct LaunchLog {
@@ -953,11 +954,13 @@ struct BatchPacker {
     const uint64_t grid = a.totalTiles < maxBlocks ? a.totalTiles : maxBlocks;
     void* args[] = {&a};
     hipError_t err = hipLaunchKernel(ks.batch[nSrcs - 1], dim3((unsigned)grid), dim3(kBlock), args, 0, stream);
+    const int nBuckets = a.nTasks;
     reset();
     if (err != hipSuccess) {
       std::fprintf(stderr, "nbx: batch kernel launch failed: %s\n", hipGetErrorString(err));
       return ncclUnhandledCudaError;
     }
+    logLaunch(kFamBatch, nSrcs, 1, nBuckets << nbx::kLaunchSegsShift);
     return ncclSuccess;
   }
 };
@@ -1204,6 +1207,7 @@ ncclResult_t launchBatchList(const KernelSet& ks, int nSrcs, const std::vector<c
       std::fprintf(stderr, "nbx: batch-list kernel launch failed: %s\n", hipGetErrorString(err));
       return ncclUnhandledCudaError;
     }
+    logLaunch(kFamBatchList, nSrcs, 1, (int)nRec << nbx::kLaunchSegsShift);
     i += nRec;
     *done = i;
   }

@@ -213,7 +213,8 @@ def test_fp8_fold_matches_torch(oracle, dtype, devop, nsrc):
 # ---------------------------------------------------------------------------
 # run order
 
-@pytest.mark.parametrize("path", ["tests/matrix/test_reduce_gpu.py", "tests/wide/test_reduce_gpu.py"])
+@pytest.mark.parametrize("path", ["tests/matrix/test_reduce_gpu.py", "tests/wide/test_reduce_gpu.py",
+                                  "tests/batch/test_reduce_gpu.py"])
 def test_gpu_files_sort_with_the_parity_core(path):
     assert gpu_order_key(path) == gpu_order_key("tests/test_reduce_gpu.py")
     assert gpu_order_key(path, "test_pack_kernels[small_packs-0]") == gpu_order_key("tests/test_reduce_gpu.py")

@@ -376,9 +376,16 @@ def test_in_place(nbx, oracle, torch_gpu):
     assert_same(ts[0].cpu().numpy(), exp, 7)
 
 
-def run_batch(nbx, oracle, torch, dtype, devop, arg, buckets, npre=0, post=False):
+def batch_records(family, launches):
+    """The launch record (include/nbx_debug.h, families 13 kernel-argument and
+    14 work-list batch) of batch launches [(source count, buckets), ...]."""
+    return [(family, nsrc, 1, n << 8) for nsrc, n in launches]
+
+
+def run_batch(nbx, oracle, torch, dtype, devop, arg, buckets, npre=0, post=False, records=None):
     """nbxReduceMultiBatch over buckets [(nsrc, ndst, count, src_off, dst_off, seed)], each
-    checked bit-exact against the oracle's single-bucket fold, guard bytes untouched."""
+    checked bit-exact against the oracle's single-bucket fold, guard bytes untouched; `records`:
+    the launch record the call has to leave."""
     dev = Dev(torch)
     st = oracle.NP_STORAGE[dtype]
     eb = np.dtype(st).itemsize
@@ -392,8 +399,12 @@ def run_batch(nbx, oracle, torch, dtype, devop, arg, buckets, npre=0, post=False
     op = nbx.DevRedOpFull()
     op.op = devop
     op.scalarArg = arg
+    nbx.launch_log_reset()
     nbx.reduce_multi_batch(calls, dtype, op, npre, post, torch.cuda.current_stream().cuda_stream)
+    log = nbx.launch_log()
     torch.cuda.synchronize()
+    if records is not None:
+        assert log == (len(records), records), f"launch record {log[1]} (of {log[0]}), wanted {records}"
     for srcs, outs, do, count in cases:
         exp = oracle.reduce_multi(srcs, dtype, devop, arg, npre, post, n_dsts=1, threads=8)[0]
         for t, _ in outs:
@@ -445,12 +456,20 @@ def test_batch_many_buckets_and_alignments(nbx, oracle, torch_gpu, dtype):
 def test_batch_table_overflow(nbx, oracle, torch_gpu):
     """More buckets than one kernel-argument table holds (101 two-source or 28
     eight-source/eight-destination records): the table is launched when full
-    and packing resumes."""
-    rng = np.random.default_rng(11)
-    buckets = [(2, 1, int(rng.integers(1, 3000)), 0, 0, 2000 + i) for i in range(150)]
-    buckets += [(8, 8, int(rng.integers(1, 3000)), 4, 4, 3000 + i) for i in range(35)]
-    run_batch(nbx, oracle, torch_gpu, 7, 0, 0, buckets)
-    run_batch(nbx, oracle, torch_gpu, 2, 4, 3, buckets[140:160], post=True)
+    and packing resumes. Kernel-argument tables only (batch mode 0): by default
+    sets this long take the work list, whose table holds them all."""
+    lib = nbx.load_library()
+    prev = lib.nbxDebugSetBatchMode(0)
+    try:
+        rng = np.random.default_rng(11)
+        buckets = [(2, 1, int(rng.integers(1, 3000)), 0, 0, 2000 + i) for i in range(150)]
+        buckets += [(8, 8, int(rng.integers(1, 3000)), 4, 4, 3000 + i) for i in range(35)]
+        run_batch(nbx, oracle, torch_gpu, 7, 0, 0, buckets,
+                  records=batch_records(13, [(2, 101), (2, 49), (8, 28), (8, 7)]))
+        run_batch(nbx, oracle, torch_gpu, 2, 4, 3, buckets[140:160], post=True,
+                  records=batch_records(13, [(2, 10), (8, 10)]))
+    finally:
+        lib.nbxDebugSetBatchMode(prev)
 
 
 @pytest.mark.parametrize("dtype,nsrc", [(7, 8), (6, 4), (9, 5), (4, 6)])
@@ -557,8 +576,13 @@ def test_batch_work_list_and_kernarg_forms(nbx, oracle, torch_gpu, mode):
         buckets = [(2, 1, int(rng.integers(1, 5000)), 0, 0, 4000 + i) for i in range(450)]
         buckets += [(8, 8, int(rng.integers(1, 20000)), 8, 8, 5000 + i) for i in range(40)]
         buckets += [(5, 2, int(rng.integers(1, 300000)), 4, 4, 6000 + i) for i in range(6)]
-        run_batch(nbx, oracle, torch_gpu, 7, 0, 0, buckets)
-        run_batch(nbx, oracle, torch_gpu, 6, 0, 0, [(8, 1, 32768, 0, 0, 7000 + i) for i in range(128)])
+        # mode 1: the 450 and the 40 as work lists (384 per launch), the six five-source buckets
+        # (<= 16, one table) in kernel arguments; mode 0: tables of 101 / 56 / 28 such buckets
+        want = {1: batch_records(14, [(2, 384), (2, 66)]) + batch_records(13, [(5, 6)]) + batch_records(14, [(8, 40)]),
+                0: batch_records(13, [(2, 101)] * 4 + [(2, 46), (5, 6), (8, 28), (8, 12)])}[mode]
+        run_batch(nbx, oracle, torch_gpu, 7, 0, 0, buckets, records=want)
+        want = {1: batch_records(14, [(8, 128)]), 0: batch_records(13, [(8, 46), (8, 46), (8, 36)])}[mode]
+        run_batch(nbx, oracle, torch_gpu, 6, 0, 0, [(8, 1, 32768, 0, 0, 7000 + i) for i in range(128)], records=want)
     finally:
         lib.nbxDebugSetBatchMode(prev)
 
@@ -605,15 +629,20 @@ def test_batch_work_list_slots_and_graph_ownership(nbx, oracle, torch_gpu):
         # slots are in flight however fast or slow the host is
         hold = lib.nbxDebugHoldStream(ctypes.c_void_p(s.cuda_stream), 60_000)
         assert hold >= 0
+        nbx.launch_log_reset()
         try:
             with torch.cuda.stream(s):
                 for _ in range(300):   # > 128 slots in flight: the rest fall back to kernel-argument tables
                     nbx.reduce_multi_batch(buckets, dtype, op, 0, False, s.cuda_stream)
         finally:
             assert lib.nbxDebugReleaseStream(hold) == 0
+        total, recs = nbx.launch_log()
         s.synchronize()
         check(host)
         assert lib.nbxDebugBatchListSlots(dev_id, 3) > fb0   # the fallback ran, and came out right
+        # one launch per call, the newest ones kernel-argument batches of all 20 buckets
+        assert total == 300 and set(recs) <= {(13, nsrc, 1, 20 << 8), (14, nsrc, 1, 20 << 8)}
+        assert recs[-1] == (13, nsrc, 1, 20 << 8)
         with torch.cuda.stream(s):
             for _ in range(20):   # each eager call returns a few completed slots to the free pool
                 nbx.reduce_multi_batch(buckets, dtype, op, 0, False, s.cuda_stream)
