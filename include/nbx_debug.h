@@ -149,7 +149,8 @@ int nbxDebugHoldStream(ncclStream_t stream, int timeoutMs);
 int nbxDebugReleaseStream(int hold);
 
 /* Launch record (test hook): every kernel pass that nbxReduceMulti /
- * nbxReduceMultiWide / nbxReduceMultiBatch launch from the calling thread, and
+ * nbxReduceMultiWide / nbxReduceMultiBatch / nbxReduceMultiWideBatch launch
+ * from the calling thread, and
  * every collective kernel a multi-rank communicator launches from it, appends
  * {family, nSrcs, unroll, flags} to a thread-local log, so a test can see
  * which kernel a call took.
@@ -190,6 +191,20 @@ int nbxDebugReleaseStream(int hold);
  * order; then, per source count ascending, that count's work-list launches
  * followed by its kernel-argument launches (the buckets no free table slot
  * was left for; all of them with work lists off or for a small set).
+ * Batched launches of nbxReduceMultiWideBatch (nbx_reduce.cc
+ * launchBatchList), one record per kernel launched, after the launch
+ * succeeded — family: 15 wide work-list batch (kWideBatchList). nSrcs: the
+ * launch's source count. unroll: 1. flags: bit 1 fp32 output, bits 8.. the
+ * buckets of that launch (buckets of count 0 are never counted). Buckets that
+ * do not go into a batch leave the records of nbxReduceMultiWide, families 6
+ * and 7. Order of one call's records: first, in bucket order, the buckets
+ * that run alone (mixed layouts, > 8 sources, 4+ sources filling the GPU
+ * alone, every bucket under launch variant 2); then, per source count
+ * ascending, that count's work-list launches followed by one family-6 launch
+ * for each of its buckets that got no table slot (arena exhausted — counted
+ * in nbxDebugBatchListSlots(dev, 3) as for the per-step batch —, a capture
+ * that cannot take a slot, batch mode 0). Batch modes 1 and 2 both mean work
+ * lists here: there is no kernel-argument form.
  * Plain host stores; the log keeps the newest 64 passes.
  * nbxDebugLaunchLog returns the number of passes since the last
  * nbxDebugLaunchLogReset() and copies the newest min(maxRecords, 64, that

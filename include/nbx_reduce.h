@@ -138,6 +138,32 @@ ncclResult_t nbxReduceMultiBatch(const nbxReduceTask* tasks, int nTasks,
                                  ncclDataType_t datatype, nbxDevRedOpFull op,
                                  int nPreOpSrcs, int postOp, ncclStream_t stream);
 
+/* Batched form of nbxReduceMultiWide: nTasks independent buckets with one
+ * source type, destination type and op, as if nbxReduceMultiWide(t.dsts,
+ * t.nDsts, t.srcs, t.nSrcs, t.count, srcType, dstType, op, nPreOpSrcs, stream)
+ * were called for every bucket t — the same arithmetic (exact widening, one
+ * unfused fp32 multiply or add per step in source order, denormals kept, one
+ * narrowing or an fp32 store), so the results are bit-identical to the
+ * per-bucket calls for every layout. Buckets of <= 8 sources whose layout
+ * nbxReduceMultiWide's pack kernel takes (sources on one misalignment modulo
+ * 16, every destination 16-byte aligned behind the head elements) run
+ * together from a work-list table, up to 384 per launch and one launch series
+ * per source count; every other bucket (mixed layouts, > 8 sources, 4+
+ * sources large enough to fill the GPU alone, launch variant 2) and any bucket
+ * that got no table slot runs as its own nbxReduceMultiWide launch — nothing
+ * waits for a slot. Buckets must be independent, as for nbxReduceMultiBatch;
+ * a destination of srcType may be one of its own bucket's sources.
+ * Type, op and scalar checks as nbxReduceMultiWide, made even for nTasks ==
+ * 0 (then a no-op); nTasks < 0 or tasks == NULL with nTasks > 0:
+ * ncclInvalidArgument. Every bucket is checked (counts, NULL pointers, element
+ * alignment, an fp32 destination overlapping one of its own sources) before
+ * anything is enqueued and before any device call; buckets of count 0 are
+ * skipped, the pointers in their arrays unexamined, as in the single call.
+ * Stream-ordered, asynchronous and graph-capturable. */
+ncclResult_t nbxReduceMultiWideBatch(const nbxReduceTask* tasks, int nTasks,
+                                     ncclDataType_t srcType, ncclDataType_t dstType,
+                                     nbxDevRedOpFull op, int nPreOpSrcs, ncclStream_t stream);
+
 /* Host-staged form of nbxReduceMulti: sources and destinations in HOST memory
  * (pinned for full speed; pageable works), the path NCCL's NET/SHM transports
  * stage through (host-pinned proxy FIFOs net.cc:735/883, /dev/shm buffers

@@ -167,6 +167,8 @@ _SIGS = {
     "nbxReduceMultiWide": [ctypes.POINTER(ctypes.c_void_p), ctypes.c_int, ctypes.POINTER(ctypes.c_void_p),
                            ctypes.c_int, ctypes.c_size_t, ctypes.c_int, ctypes.c_int, DevRedOpFull, ctypes.c_int,
                            ctypes.c_void_p],
+    "nbxReduceMultiWideBatch": [ctypes.POINTER(ReduceTask), ctypes.c_int, ctypes.c_int, ctypes.c_int, DevRedOpFull,
+                                ctypes.c_int, ctypes.c_void_p],
     "nbxSetLaunchConfig": [ctypes.c_int, ctypes.c_int],
     "nbxGetLaunchConfig": [ctypes.POINTER(ctypes.c_int), ctypes.POINTER(ctypes.c_int)],
     "nbxKernelCount": [],
@@ -348,6 +350,7 @@ class LaunchFamily(enum.IntEnum):        # include/nbx_debug.h nbxDebugLaunchLog
     SimpleRing = 12
     BatchKernarg = 13     # nbxReduceMultiBatch launches: flags bits 8.. = buckets of the launch
     BatchList = 14
+    WideBatchList = 15    # nbxReduceMultiWideBatch launches: flags bit 1 = fp32 output, bits 8.. = buckets
 
 
 LAUNCH_DYNAMIC, LAUNCH_OUT32, LAUNCH_PART_FIRST = 1, 2, 4
@@ -402,9 +405,8 @@ def reduce_multi_wide(dsts: Sequence[int], srcs: Sequence[int], count: int, src_
            "nbxReduceMultiWide")
 
 
-def reduce_multi_batch_raw(buckets: Sequence[tuple], dtype: int, op: DevRedOpFull, n_pre_op_srcs: int = 0,
-                           post_op: bool = False, stream: int = 0) -> int:
-    """Call nbxReduceMultiBatch over buckets [(dsts, srcs, count), ...]; returns the code."""
+def _reduce_tasks(buckets: Sequence[tuple]) -> tuple:
+    """(nbxReduceTask array, the pointer arrays it refers to) of buckets [(dsts, srcs, count), ...]."""
     keep = []
     tasks = (ReduceTask * max(1, len(buckets)))()
     for i, (dsts, srcs, count) in enumerate(buckets):
@@ -413,8 +415,31 @@ def reduce_multi_batch_raw(buckets: Sequence[tuple], dtype: int, op: DevRedOpFul
         keep += [d, s]
         tasks[i] = ReduceTask(ctypes.cast(d, ctypes.POINTER(ctypes.c_void_p)), len(dsts),
                               ctypes.cast(s, ctypes.POINTER(ctypes.c_void_p)), len(srcs), int(count))
+    return tasks, keep
+
+
+def reduce_multi_batch_raw(buckets: Sequence[tuple], dtype: int, op: DevRedOpFull, n_pre_op_srcs: int = 0,
+                           post_op: bool = False, stream: int = 0) -> int:
+    """Call nbxReduceMultiBatch over buckets [(dsts, srcs, count), ...]; returns the code."""
+    tasks, _keep = _reduce_tasks(buckets)
     return load_library().nbxReduceMultiBatch(tasks, len(buckets), int(dtype), op, int(n_pre_op_srcs),
                                               int(bool(post_op)), ctypes.c_void_p(int(stream)))
+
+
+def reduce_multi_wide_batch_raw(buckets: Sequence[tuple], src_type: int, dst_type: int, op: DevRedOpFull,
+                                n_pre_op_srcs: int = 0, stream: int = 0) -> int:
+    """Call nbxReduceMultiWideBatch over buckets [(dsts, srcs, count), ...]; returns the code."""
+    tasks, _keep = _reduce_tasks(buckets)
+    return load_library().nbxReduceMultiWideBatch(tasks, len(buckets), int(src_type), int(dst_type), op,
+                                                  int(n_pre_op_srcs), ctypes.c_void_p(int(stream)))
+
+
+def reduce_multi_wide_batch(buckets: Sequence[tuple], src_type: int, dst_type: int, op: DevRedOpFull,
+                            n_pre_op_srcs: int = 0, stream: int = 0) -> None:
+    """Independent buckets [(dsts, srcs, count), ...] of f16 / bf16 / fp8 sources summed in fp32 into
+    destinations of `src_type` or fp32, as batched launches (one nbxReduceMultiWide per bucket in effect)."""
+    _check(reduce_multi_wide_batch_raw(buckets, src_type, dst_type, op, n_pre_op_srcs, stream),
+           "nbxReduceMultiWideBatch")
 
 
 def reduce_multi_batch(buckets: Sequence[tuple], dtype: int, op: DevRedOpFull, n_pre_op_srcs: int = 0,

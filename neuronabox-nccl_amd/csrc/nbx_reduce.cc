@@ -292,7 +292,8 @@ constexpr int kLaunchLogCap = 64;
 enum LaunchFamily {
   kFamSmallPacks = 1, kFamBigPacks = 2, kFamElts = 3, kFamShiftedLds = 4, kFamShifted = 5, kFamWidePacks = 6,
   kFamWideElts = 7,
-  kFamBatch = 13, kFamBatchList = 14   // batched buckets: flags bits kLaunchSegsShift.. = buckets of the launch
+  kFamBatch = 13, kFamBatchList = 14,   // batched buckets: flags bits kLaunchSegsShift.. = buckets of the launch
+  kFamWideBatchList = 15                // the same for nbxReduceMultiWideBatch (bit 1: fp32 output)
 };
 enum LaunchFlag { kLaunchDynamic = 1, kLaunchOut32 = 2, kLaunchPartFirst = 4 };
 struct LaunchLog {
@@ -809,20 +810,24 @@ ncclResult_t launchWidePass(const WideSet& ws, bool out32, bool partFirst, bool 
   return ncclSuccess;
 }
 
-ncclResult_t reduceMultiWideImpl(void* const* dsts, int nDsts, const void* const* srcs, int nSrcs, size_t count,
-                                 ncclDataType_t srcType, ncclDataType_t dstType, nbxDevRedOpFull op, int nPreOpSrcs,
-                                 ncclStream_t stream) {
-  if (nSrcs < 1 || nSrcs > NBX_MAX_SRCS || nDsts < 1 || nDsts > NBX_MAX_DSTS) return ncclInvalidArgument;
-  if (srcs == nullptr || dsts == nullptr) return ncclInvalidArgument;
+// Type, op and scalar checks of the fp32-accumulating sums, shared by the
+// single and batched entry points.
+ncclResult_t checkWideOp(ncclDataType_t srcType, ncclDataType_t dstType, const nbxDevRedOpFull& op) {
   const int st = (int)srcType, dt = (int)dstType;
   if (st < 0 || st >= kNumTypes || !wideTable()[st].valid) return ncclInvalidArgument;   // f16, bf16, fp8 only
   if (dt != st && dt != (int)ncclFloat32) return ncclInvalidArgument;
   if (op.op != nbxDevSum && op.op != nbxDevPreMulSum) return ncclInvalidArgument;
-  const bool pre = op.op == nbxDevPreMulSum;
-  if (pre && op.scalarArgIsPtr && (op.scalarArg == 0 || (op.scalarArg & 3u) != 0)) return ncclInvalidArgument;
+  if (op.op == nbxDevPreMulSum && op.scalarArgIsPtr && (op.scalarArg == 0 || (op.scalarArg & 3u) != 0))
+    return ncclInvalidArgument;
+  return ncclSuccess;
+}
+
+// Their per-bucket checks (count == 0 accepts anything but NULL arrays).
+ncclResult_t checkWideBucket(const WideSet& ws, bool out32, void* const* dsts, int nDsts, const void* const* srcs,
+                             int nSrcs, size_t count) {
+  if (nSrcs < 1 || nSrcs > NBX_MAX_SRCS || nDsts < 1 || nDsts > NBX_MAX_DSTS) return ncclInvalidArgument;
+  if (srcs == nullptr || dsts == nullptr) return ncclInvalidArgument;
   if (count == 0) return ncclSuccess;
-  const WideSet& ws = wideTable()[st];
-  const bool out32 = dt != st;
   const size_t eb = (size_t)ws.eltBytes, deb = out32 ? sizeof(float) : eb;
   for (int s = 0; s < nSrcs; s++)
     if (srcs[s] == nullptr || ((uintptr_t)srcs[s] % eb) != 0) return ncclInvalidArgument;
@@ -834,17 +839,43 @@ ncclResult_t reduceMultiWideImpl(void* const* dsts, int nDsts, const void* const
     for (int d = 0; d < nDsts; d++)
       for (int s = 0; s < nSrcs; s++)
         if (overlaps(dsts[d], count * deb, srcs[s], count * eb)) return ncclInvalidArgument;
+  return ncclSuccess;
+}
+
+// Pack-kernel layout: the sources share one misalignment modulo 16, and behind
+// the head elements that align them every destination is 16-byte aligned.
+// *head: those elements, at most count.
+bool widePackLayout(size_t eb, size_t deb, void* const* dsts, int nDsts, const void* const* srcs, int nSrcs,
+                    size_t count, size_t* head) {
+  const unsigned mis = (unsigned)((uintptr_t)srcs[0] & 15u);
+  size_t h = mis ? (size_t)(16u - mis) / eb : 0;
+  bool fast = true;
+  for (int s = 1; s < nSrcs; s++) fast &= (((uintptr_t)srcs[s] & 15u) == mis);
+  for (int d = 0; d < nDsts; d++) fast &= ((((uintptr_t)dsts[d] + h * deb) & 15u) == 0);
+  *head = h > count ? count : h;
+  return fast;
+}
+
+ncclResult_t reduceMultiWideImpl(void* const* dsts, int nDsts, const void* const* srcs, int nSrcs, size_t count,
+                                 ncclDataType_t srcType, ncclDataType_t dstType, nbxDevRedOpFull op, int nPreOpSrcs,
+                                 ncclStream_t stream) {
+  if (nSrcs < 1 || nSrcs > NBX_MAX_SRCS || nDsts < 1 || nDsts > NBX_MAX_DSTS) return ncclInvalidArgument;
+  if (srcs == nullptr || dsts == nullptr) return ncclInvalidArgument;
+  ncclResult_t cr = checkWideOp(srcType, dstType, op);
+  if (cr != ncclSuccess) return cr;
+  if (count == 0) return ncclSuccess;
+  const int st = (int)srcType;
+  const bool pre = op.op == nbxDevPreMulSum;
+  const WideSet& ws = wideTable()[st];
+  const bool out32 = (int)dstType != st;
+  const size_t eb = (size_t)ws.eltBytes, deb = out32 ? sizeof(float) : eb;
+  cr = checkWideBucket(ws, out32, dsts, nDsts, srcs, nSrcs, count);
+  if (cr != ncclSuccess) return cr;
   if (nPreOpSrcs < 0) nPreOpSrcs = 0;
   hipStream_t strm = (hipStream_t)stream;
 
-  // pack kernel: the sources share one misalignment modulo 16, and behind the
-  // head elements that align them every destination is 16-byte aligned
-  const unsigned mis = (unsigned)((uintptr_t)srcs[0] & 15u);
-  size_t head = mis ? (size_t)(16u - mis) / eb : 0;
-  bool fast = true;
-  for (int s = 1; s < nSrcs; s++) fast &= (((uintptr_t)srcs[s] & 15u) == mis);
-  for (int d = 0; d < nDsts; d++) fast &= ((((uintptr_t)dsts[d] + head * deb) & 15u) == 0);
-  if (head > count) head = count;
+  size_t head = 0;
+  const bool fast = widePackLayout(eb, deb, dsts, nDsts, srcs, nSrcs, count, &head);
 
   auto maskFor = [&](int first, int n, int slot0) {   // sources [first, first + n) sit in slots slot0 ...
     uint32_t m = 0;
@@ -1127,10 +1158,13 @@ int listSlotCount(int dev, int state) {
 
 // Launches the buckets of one source count as work-list kernels (as many
 // launches as slots they need). Returns the number of buckets launched from
-// the front of `ts` (fewer than ts.size() when no slot was free).
-ncclResult_t launchBatchList(const KernelSet& ks, int nSrcs, const std::vector<const nbxReduceTask*>& ts,
-                             const nbxDevRedOpFull& op, uint32_t preMask, int postOp, int acq, hipStream_t st,
-                             size_t* done) {
+// the front of `ts` (fewer than ts.size() when no slot was free). One record
+// writer for both batched entry points: `kernel` is kReduceBatchList's or
+// kWideBatchList's instantiation for nSrcs, eb the sources' element size (the
+// head is counted in source elements), family / flagBits its launch record.
+ncclResult_t launchBatchList(const void* kernel, int eb, int family, int flagBits, int nSrcs,
+                             const std::vector<const nbxReduceTask*>& ts, const nbxDevRedOpFull& op, uint32_t preMask,
+                             int postOp, int acq, hipStream_t st, size_t* done) {
   *done = 0;
   const int dev = launchDevice(st);
   hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
@@ -1146,7 +1180,6 @@ ncclResult_t launchBatchList(const KernelSet& ks, int nSrcs, const std::vector<c
   // config-C bucket set (profiles/r2/batch_list_chunk_r2p.jsonl)
   static const uint64_t chunkEnv = (uint64_t)envInt("NBX_BATCH_CHUNK", 4);
   const uint64_t chunk = chunkEnv < 1 ? 1 : chunkEnv;
-  const int eb = ks.eltBytes;
   const uint64_t epp = (uint64_t)(16 / eb);
   static_assert(sizeof(BatchListArgs) <= 4096, "work-list arguments must fit the kernel-argument segment");
   BatchListArgs a;
@@ -1201,13 +1234,13 @@ ncclResult_t launchBatchList(const KernelSet& ks, int nSrcs, const std::vector<c
     publishListSlot(dev, (const volatile uint32_t*)(recs + nRec * (size_t)recWords - 1));
     void* args[] = {&a};
     const hipError_t err =
-        hipLaunchKernel(ks.batchList[nSrcs - 1], dim3((unsigned)G), dim3(kBlock), args, 0, st);
+        hipLaunchKernel(kernel, dim3((unsigned)G), dim3(kBlock), args, 0, st);
     releaseListSlot(dev, slot, st, capturing ? graph : nullptr, err == hipSuccess);
     if (err != hipSuccess) {
       std::fprintf(stderr, "nbx: batch-list kernel launch failed: %s\n", hipGetErrorString(err));
       return ncclUnhandledCudaError;
     }
-    logLaunch(kFamBatchList, nSrcs, 1, (int)nRec << nbx::kLaunchSegsShift);
+    logLaunch(family, nSrcs, 1, flagBits | ((int)nRec << nbx::kLaunchSegsShift));
     i += nRec;
     *done = i;
   }
@@ -1277,7 +1310,8 @@ ncclResult_t reduceMultiBatchImpl(const nbxReduceTask* tasks, int nTasks, ncclDa
       fitsKernarg = words <= (size_t)kBatchWords;
     }
     if (useList && !fitsKernarg) {
-      r = launchBatchList(ks, ns, lists[q], op, mask, post, acq, st, &done);
+      r = launchBatchList(ks.batchList[q], ks.eltBytes, kFamBatchList, 0, ns, lists[q], op, mask, post, acq, st,
+                          &done);
       if (r != ncclSuccess) return r;
     }
     if (done == lists[q].size()) continue;
@@ -1289,6 +1323,82 @@ ncclResult_t reduceMultiBatchImpl(const nbxReduceTask* tasks, int nTasks, ncclDa
     }
     r = packers[q]->flush();
     if (r != ncclSuccess) return r;
+  }
+  return ncclSuccess;
+}
+
+// nbxReduceMultiWideBatch: the buckets nbxReduceMultiWide's pack kernel would
+// take go into work-list launches of kWideBatchList per source count; every
+// other bucket, and every bucket no table slot was left for, is one
+// nbxReduceMultiWide launch. There is no kernel-argument form, so batch modes
+// 1 and 2 both mean work lists.
+ncclResult_t reduceMultiWideBatchImpl(const nbxReduceTask* tasks, int nTasks, ncclDataType_t srcType,
+                                      ncclDataType_t dstType, nbxDevRedOpFull op, int nPreOpSrcs,
+                                      ncclStream_t stream) {
+  ncclResult_t r = checkWideOp(srcType, dstType, op);
+  if (r != ncclSuccess) return r;
+  if (nTasks < 0 || (nTasks > 0 && tasks == nullptr)) return ncclInvalidArgument;
+  const int stype = (int)srcType;
+  const WideSet& ws = wideTable()[stype];
+  const bool out32 = (int)dstType != stype;
+  const size_t eb = (size_t)ws.eltBytes, deb = out32 ? sizeof(float) : eb;
+  // every bucket is checked before anything is enqueued
+  bool any = false;
+  for (int i = 0; i < nTasks; i++) {
+    r = checkWideBucket(ws, out32, tasks[i].dsts, tasks[i].nDsts, tasks[i].srcs, tasks[i].nSrcs, tasks[i].count);
+    if (r != ncclSuccess) return r;
+    any |= tasks[i].count != 0;
+  }
+  if (!any) return ncclSuccess;
+  if (nPreOpSrcs < 0) nPreOpSrcs = 0;
+  const bool pre = op.op == nbxDevPreMulSum;
+  hipStream_t st = (hipStream_t)stream;
+  // single buckets first, in bucket order: layouts the pack kernel does not
+  // take, > 8 sources (passes through the fp32 partial), everything under
+  // launch variant 2, and buckets of 4+ sources whose body gives every CU an
+  // unrolled tile alone (the per-step batch's rule; variant 1 batches those too)
+  const int force = g_variant.load(std::memory_order_relaxed);
+  const uint64_t cus = (uint64_t)cuCount(launchDevice(st));
+  std::vector<const nbxReduceTask*> lists[kMaxKSrcs];
+  for (int i = 0; i < nTasks; i++) {
+    const nbxReduceTask& t = tasks[i];
+    if (t.count == 0) continue;
+    size_t head = 0;
+    bool single = force == 2 || t.nSrcs > kMaxKSrcs || t.count > kBatchCountMask ||
+                  !widePackLayout(eb, deb, t.dsts, t.nDsts, t.srcs, t.nSrcs, t.count, &head);
+    if (!single && force == 0 && t.nSrcs > 3)
+      single = (t.count - head) / (16 / eb) >= (uint64_t)wideUnroll(t.nSrcs) * kBlock * cus;
+    if (single) {
+      r = reduceMultiWideImpl(t.dsts, t.nDsts, t.srcs, t.nSrcs, t.count, srcType, dstType, op, nPreOpSrcs, stream);
+      if (r != ncclSuccess) return r;
+      continue;
+    }
+    lists[t.nSrcs - 1].push_back(&t);
+  }
+  // the kernel's scalar is an fp32 value, and only PreMulSum has one
+  nbxDevRedOpFull lop = op;
+  if (!pre) lop.scalarArg = 0, lop.scalarArgIsPtr = 0;
+  else if (!lop.scalarArgIsPtr) lop.scalarArg &= 0xffffffffull;
+  const bool useList = batchListEnabled();
+  for (int q = 0; q < kMaxKSrcs; q++) {
+    if (lists[q].empty()) continue;
+    const int ns = q + 1;
+    uint32_t mask = 0;
+    if (pre)
+      for (int s = 0; s < ns; s++)
+        if (s < nPreOpSrcs) mask |= 1u << s;
+    size_t done = 0;
+    if (useList) {
+      r = launchBatchList(ws.batchList[out32 ? 1 : 0][q], (int)eb, kFamWideBatchList, out32 ? kLaunchOut32 : 0, ns,
+                          lists[q], lop, mask, 0, 0, st, &done);
+      if (r != ncclSuccess) return r;
+    }
+    // the rest one launch each (work lists off, or no table slot free)
+    for (size_t j = done; j < lists[q].size(); j++) {
+      const nbxReduceTask& t = *lists[q][j];
+      r = reduceMultiWideImpl(t.dsts, t.nDsts, t.srcs, t.nSrcs, t.count, srcType, dstType, op, nPreOpSrcs, stream);
+      if (r != ncclSuccess) return r;
+    }
   }
   return ncclSuccess;
 }
@@ -1330,6 +1440,14 @@ __attribute__((visibility("default"))) ncclResult_t nbxReduceMultiWide(void* con
                                                                         ncclDataType_t dstType, nbxDevRedOpFull op,
                                                                         int nPreOpSrcs, ncclStream_t stream) {
   return reduceMultiWideImpl(dsts, nDsts, srcs, nSrcs, count, srcType, dstType, op, nPreOpSrcs, stream);
+}
+
+__attribute__((visibility("default"))) ncclResult_t nbxReduceMultiWideBatch(const nbxReduceTask* tasks, int nTasks,
+                                                                             ncclDataType_t srcType,
+                                                                             ncclDataType_t dstType,
+                                                                             nbxDevRedOpFull op, int nPreOpSrcs,
+                                                                             ncclStream_t stream) {
+  return reduceMultiWideBatchImpl(tasks, nTasks, srcType, dstType, op, nPreOpSrcs, stream);
 }
 
 __attribute__((visibility("default"))) ncclResult_t nbxSetLaunchConfig(int blocksPerCU, int variant) {

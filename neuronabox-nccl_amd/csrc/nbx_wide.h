@@ -22,6 +22,8 @@
 // PART: source 0 is the fp32 partial of an earlier pass (more than 8 sources
 // fold in passes of 8 + 7 + 7 ...; the partial is never narrowed, so the
 // result is the single fp32 left fold over all sources).
+// A third family, kWideBatchList<W, NSRC, OUT32>, runs many buckets from a
+// work-list table in one launch (nbxReduceMultiWideBatch; below).
 #pragma once
 #include "nbx_kernels.h"   // ldPack / stPack, forEachTile
 
@@ -276,6 +278,114 @@ __global__ __launch_bounds__(kBlock) void kWideElts(KArgs a) {
 }
 
 // ---------------------------------------------------------------------------
+// Batched buckets (nbxReduceMultiWideBatch): kReduceBatchList's scheduler
+// (nbx_kernels.h — records from the table in BatchListArgs::recs, running tile
+// totals in the kernel arguments, chunks of consecutive tiles round-robin, the
+// 64-wide ballot search, no LDS and no barrier) around kWidePacks' per-tile
+// work at U = 1. The record layout is the per-step one; `head` counts
+// elements (<= 15, fp8), so an fp32 destination's body starts head floats in.
+// Buckets of more than 8 sources never enter a batch: no partial-first form.
+
+// One head or tail element: wideElt's arithmetic, the source count a
+// template argument (as batchElt).
+template <class W, int NSRC, bool OUT32>
+__device__ __forceinline__ void wideBatchElt(const typename W::Elt* const (&src)[NSRC], void* const (&dst)[kMaxKDsts],
+                                             int nDsts, uint32_t preMask, float sc, uint64_t i) {
+  using E = typename W::Elt;
+  float acc = W::wide(src[0][i]);
+  if (preMask & 1u) acc = acc * sc;
+#pragma unroll
+  for (int s = 1; s < NSRC; s++) {
+    float v = W::wide(src[s][i]);
+    if ((preMask >> s) & 1u) v = v * sc;
+    acc = acc + v;
+  }
+#pragma unroll
+  for (int d = 0; d < kMaxKDsts; d++) {
+    if (d < nDsts) {
+      if constexpr (OUT32) ((float*)dst[d])[i] = acc;
+      else ((E*)dst[d])[i] = W::narrow(acc);
+    }
+  }
+}
+
+template <class W, int NSRC, bool OUT32>
+__global__ __launch_bounds__(kBlock) void kWideBatchList(BatchListArgs a) {
+  using E = typename W::Elt;
+  constexpr int EPP = W::kEPP, Q = EPP / 4;
+  const float sc = a.argPtr != nullptr ? *(const float*)a.argPtr : __uint_as_float((uint32_t)a.arg);
+  const uint32_t preMask = a.preMask;
+  const bool pre = preMask != 0;   // uniform per launch: the fold is never chosen per element
+  float mul[NSRC];
+#pragma unroll
+  for (int s = 0; s < NSRC; s++) mul[s] = ((preMask >> s) & 1u) ? sc : 1.0f;
+  const uint64_t T = a.totalTiles, C = a.chunk, step = (uint64_t)gridDim.x * C;
+  const int nRecs = a.nRecs, lane = (int)(threadIdx.x & 63u);
+  int k = -1;
+  uint64_t tBegin = 0, tEnd = 0, nElts = 0, n = 0;
+  int nDsts = 1, head = 0;
+  const E* sb[NSRC];
+  void* db[kMaxKDsts];
+  const u32x4* src[NSRC];
+  u32x4* dst[kMaxKDsts];
+  for (uint64_t c0 = (uint64_t)blockIdx.x * C; c0 < T; c0 += step) {
+    const uint64_t c1 = c0 + C < T ? c0 + C : T;
+    for (uint64_t tile = c0; tile < c1; tile++) {
+      if (tile >= tEnd) {   // next bucket holding this tile (uniform per wave)
+        for (int base = k + 1;; base += 64) {
+          const int idx = base + lane;
+          const uint64_t e = idx < nRecs ? (uint64_t)a.tileEnd[idx] : ~0ull;
+          const uint64_t m = __ballot(e > tile);
+          if (m != 0) {
+            k = __builtin_amdgcn_readfirstlane(base + (int)__builtin_ctzll(m));
+            break;
+          }
+        }
+        const uint64_t* r = a.recs + (uint64_t)k * a.recWords;
+        tBegin = r[0];
+        tEnd = r[1];
+        const uint64_t meta = r[2];
+        nDsts = (int)(meta >> 60);
+        nElts = meta & kBatchCountMask;
+        head = (int)((meta >> 56) & 15u);
+        n = (nElts - (uint64_t)head) / EPP;
+#pragma unroll
+        for (int s = 0; s < NSRC; s++) {
+          sb[s] = (const E*)r[3 + s];
+          src[s] = (const u32x4*)(sb[s] + head);
+        }
+#pragma unroll
+        for (int d = 0; d < kMaxKDsts; d++) {
+          db[d] = (void*)r[3 + NSRC + (d < nDsts ? d : 0)];
+          dst[d] = (u32x4*)((char*)db[d] + (uint64_t)head * (OUT32 ? sizeof(float) : sizeof(E)));
+        }
+      }
+      const uint64_t p = (tile - tBegin) * kBatchTilePacks + threadIdx.x;
+      if (p < n) {
+        u32x4 part[1][Q];   // no partial-first form: unused
+        u32x4 v[NSRC][1];
+#pragma unroll
+        for (int s = 0; s < NSRC; s++) v[s][0] = ldPack(src[s] + p);
+        // every load issued before the fold starts, as in kWidePacks (without
+        // this the widening of the first sources is scheduled between the
+        // loads, and a flat load's wait is a wait for all of them)
+        __builtin_amdgcn_sched_barrier(0);
+        if (pre) wideFoldStore<W, NSRC, 1, OUT32, false, true>(part, v, mul, dst, nDsts, p);
+        else wideFoldStore<W, NSRC, 1, OUT32, false, false>(part, v, mul, dst, nDsts, p);
+      }
+      if (tile == tEnd - 1) {   // the bucket's last tile: its head and tail elements
+        const uint64_t tailStart = (uint64_t)head + n * EPP;
+        const int tail = (int)(nElts - tailStart);
+        const int th = (int)threadIdx.x;
+        if (th < head) wideBatchElt<W, NSRC, OUT32>(sb, db, nDsts, preMask, sc, (uint64_t)th);
+        else if (th < head + tail)
+          wideBatchElt<W, NSRC, OUT32>(sb, db, nDsts, preMask, sc, tailStart + (uint64_t)(th - head));
+      }
+    }
+  }
+}
+
+// ---------------------------------------------------------------------------
 // Launch table for one source type (WideSet, nbx_kargs.h).
 
 template <class W, bool OUT32, int... I, int... J>
@@ -289,6 +399,12 @@ void fillWidePacks(WideSet& ws, std::integer_sequence<int, I...>, std::integer_s
   }
 }
 
+template <class W, bool OUT32, int... I>
+void fillWideBatch(WideSet& ws, std::integer_sequence<int, I...>) {
+  const void* list[] = {(const void*)&kWideBatchList<W, I + 1, OUT32>...};
+  for (int i = 0; i < kMaxKSrcs; i++) ws.batchList[OUT32 ? 1 : 0][i] = list[i];
+}
+
 template <class Ty>
 WideSet makeWideSet(int blocksPerCU) {
   using W = WideTy<Ty>;
@@ -297,6 +413,8 @@ WideSet makeWideSet(int blocksPerCU) {
   constexpr std::make_integer_sequence<int, kMaxKSrcs - 1> fromTwo{};
   fillWidePacks<W, false>(ws, all, fromTwo);
   fillWidePacks<W, true>(ws, all, fromTwo);
+  fillWideBatch<W, false>(ws, all);
+  fillWideBatch<W, true>(ws, all);
   ws.elts[0][0] = (const void*)&kWideElts<W, false, false>;
   ws.elts[0][1] = (const void*)&kWideElts<W, false, true>;
   ws.elts[1][0] = (const void*)&kWideElts<W, true, false>;
