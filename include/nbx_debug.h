@@ -136,6 +136,30 @@ int nbxDebugBatchListSlots(int device, int state);
  * only query. Returns the threshold in force before the call. */
 int nbxDebugSetDynMinTiles(int tilesPerWorkgroup);
 
+/* Threshold of the fp32-accumulating sums' realigning kernel
+ * (nbxReduceMultiWide, kWideShiftedLds): a call outside the pack layout whose
+ * destinations share one address modulo 16 takes it from this many elements,
+ * the element kernel below (default 2097152, the crossover measured by
+ * scripts/ab_wide_shift.py on an MI355X, profiles/r9/ab_wide_shift_mi355x.txt;
+ * env NBX_WIDE_SHIFT_MIN_ELTS; 1 sends every such call to the realigning
+ * kernel). Values < 1 only query. Returns the threshold in force before the
+ * call. */
+long long nbxDebugSetWideShiftMinElts(long long elts);
+
+/* The layout nbxReduceMultiWide decides once per call, from the pointer
+ * values alone (no device call, nothing dereferenced): 0 elements
+ * (kWideElts), 1 packs (kWidePacks: every source on one misalignment modulo
+ * 16, every destination 16-byte aligned behind the head elements that align
+ * the sources), 2 realigning (kWideShiftedLds: any other layout whose
+ * destinations share one address modulo 16, from the threshold above), -1 bad
+ * arguments (types, counts of pointers, NULL or a pointer off its element
+ * size). *head (may be NULL): the elements folded one by one in front of the
+ * 16-byte body, at most count — those that align the sources (packs) or the
+ * destinations (realigning; < 16 / destination element size), 0 for the
+ * element kernel. The launch variant does not enter. */
+int nbxDebugWideLayout(void* const* dsts, int nDsts, const void* const* srcs, int nSrcs, size_t count,
+                       ncclDataType_t srcType, ncclDataType_t dstType, size_t* head);
+
 /* Per-stream counters allocated so far on `device` by the dynamic schedules
  * (which: 0 = big-tile reduce's tile counters, 1 = realigning kernel's class
  * counters); keyed by stream handle (nbx_reduce.cc). -1 bad device. */
@@ -156,7 +180,9 @@ int nbxDebugReleaseStream(int hold);
  * which kernel a call took.
  * Reduction core — family: 1 small-tile packs, 2 big-tile packs,
  * 3 elements, 4 realigning LDS-DMA (one kernel per source count), 5 realigning
- * run-time source count, 6 wide packs, 7 wide elements. nSrcs: the pass's
+ * run-time source count, 6 wide packs, 7 wide elements, 16 wide realigning
+ * LDS-DMA (kWideShiftedLds, one kernel per source count; unroll 2 from 3
+ * sources, else 1; never dynamic). nSrcs: the pass's
  * sources (a later pass of a > 8-source call counts its partial). unroll:
  * packs per lane per source and tile (1 for the element kernels). flags:
  * bit 0 dynamic tile schedule, bit 1 fp32 output (wide), bit 2 the first
@@ -196,8 +222,10 @@ int nbxDebugReleaseStream(int hold);
  * succeeded — family: 15 wide work-list batch (kWideBatchList). nSrcs: the
  * launch's source count. unroll: 1. flags: bit 1 fp32 output, bits 8.. the
  * buckets of that launch (buckets of count 0 are never counted). Buckets that
- * do not go into a batch leave the records of nbxReduceMultiWide, families 6
- * and 7. Order of one call's records: first, in bucket order, the buckets
+ * do not go into a batch leave the records of nbxReduceMultiWide, families 6,
+ * 7 and 16 (a bucket in the realigning layout is family 16 from the threshold
+ * of nbxDebugSetWideShiftMinElts, family 7 below it, in the same place of the
+ * order). Order of one call's records: first, in bucket order, the buckets
  * that run alone (mixed layouts, > 8 sources, 4+ sources filling the GPU
  * alone, every bucket under launch variant 2); then, per source count
  * ascending, that count's work-list launches followed by one family-6 launch

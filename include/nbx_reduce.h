@@ -100,9 +100,17 @@ ncclResult_t nbxReduceMulti(void* const* dsts, int nDsts,
  * (in place); an fp32 destination whose range overlaps any source range is
  * ncclInvalidArgument. 16-byte packs when the sources share one misalignment
  * modulo 16 and every destination is 16-byte aligned behind the head elements
- * that align them (an fp32 destination: (dst + 4 * head) % 16 == 0); any other
- * layout runs one element per lane — there is no realigning (LDS-DMA) path
- * here. More than 8 sources fold in ordered passes through an fp32 partial
+ * that align them (an fp32 destination: (dst + 4 * head) % 16 == 0). Any other
+ * layout whose destinations share one address modulo 16 — sources on
+ * misalignments of their own, such as the blocks of a reduce-scatter whose
+ * count is no multiple of a pack — runs the realigning kernel from
+ * NBX_WIDE_SHIFT_MIN_ELTS elements (default 2097152, the measured crossover):
+ * 16-byte packs on the destinations' side, the sources staged through LDS by
+ * LDS-DMA and realigned on the way out, 2.3-8.0 times the element rate and
+ * 85-113 % of the pack rate at 256 MiB per input. Destinations on different
+ * alignments, and shorter calls, run one element per lane. The result is the
+ * same bits whichever kernel runs. More than 8 sources fold in ordered passes
+ * through an fp32 partial
  * (dsts[0] for an fp32 output, else stream-ordered scratch of 4 * count
  * bytes), so the result is still the single fp32 left fold.
  * Stream-ordered, asynchronous and graph-capturable. */
@@ -150,7 +158,9 @@ ncclResult_t nbxReduceMultiBatch(const nbxReduceTask* tasks, int nTasks,
  * together from a work-list table, up to 384 per launch and one launch series
  * per source count; every other bucket (mixed layouts, > 8 sources, 4+
  * sources large enough to fill the GPU alone, launch variant 2) and any bucket
- * that got no table slot runs as its own nbxReduceMultiWide launch — nothing
+ * that got no table slot runs as its own nbxReduceMultiWide launch — the
+ * realigning kernel where that call would take it, the element kernel
+ * otherwise; the work-list table stays pack-layout only — and nothing
  * waits for a slot. Buckets must be independent, as for nbxReduceMultiBatch;
  * a destination of srcType may be one of its own bucket's sources.
  * Type, op and scalar checks as nbxReduceMultiWide, made even for nTasks ==

@@ -222,6 +222,13 @@ def load_library(path: Optional[str] = None) -> ctypes.CDLL:
     lib.nbxDebugLaunchLog.restype = ctypes.c_int
     lib.nbxDebugLaunchLogReset.argtypes = []
     lib.nbxDebugLaunchLogReset.restype = None
+    # test hooks of the wide sums' dispatch: the realigning threshold and the layout function
+    lib.nbxDebugSetWideShiftMinElts.argtypes = [ctypes.c_longlong]
+    lib.nbxDebugSetWideShiftMinElts.restype = ctypes.c_longlong
+    lib.nbxDebugWideLayout.argtypes = [ctypes.POINTER(ctypes.c_void_p), ctypes.c_int, ctypes.POINTER(ctypes.c_void_p),
+                                       ctypes.c_int, ctypes.c_size_t, ctypes.c_int, ctypes.c_int,
+                                       ctypes.POINTER(ctypes.c_size_t)]
+    lib.nbxDebugWideLayout.restype = ctypes.c_int
     if path is None:
         _lib = lib
     return lib
@@ -351,6 +358,7 @@ class LaunchFamily(enum.IntEnum):        # include/nbx_debug.h nbxDebugLaunchLog
     BatchKernarg = 13     # nbxReduceMultiBatch launches: flags bits 8.. = buckets of the launch
     BatchList = 14
     WideBatchList = 15    # nbxReduceMultiWideBatch launches: flags bit 1 = fp32 output, bits 8.. = buckets
+    WideRealignLds = 16   # nbxReduceMultiWide's realigning kernel (kWideShiftedLds)
 
 
 LAUNCH_DYNAMIC, LAUNCH_OUT32, LAUNCH_PART_FIRST = 1, 2, 4
@@ -403,6 +411,27 @@ def reduce_multi_wide(dsts: Sequence[int], srcs: Sequence[int], count: int, src_
     one rounding at the end instead of one per source. The PreMulSum scalar is an fp32 value."""
     _check(reduce_multi_wide_raw(dsts, srcs, count, src_type, dst_type, op, n_pre_op_srcs, stream),
            "nbxReduceMultiWide")
+
+
+WIDE_LAYOUT_ELEMENTS, WIDE_LAYOUT_PACKS, WIDE_LAYOUT_REALIGN = 0, 1, 2   # nbxDebugWideLayout
+WIDE_SHIFT_MIN_ELTS_DEFAULT = 2097152   # the measured crossover (include/nbx_debug.h); env NBX_WIDE_SHIFT_MIN_ELTS
+
+
+def set_wide_shift_min_elts(elts: int = 0) -> int:
+    """nbxDebugSetWideShiftMinElts: elements from which a realigning layout takes kWideShiftedLds;
+    values < 1 only query. Returns the threshold in force before the call."""
+    return int(load_library().nbxDebugSetWideShiftMinElts(int(elts)))
+
+
+def wide_layout(dsts: Sequence[int], srcs: Sequence[int], count: int, src_type: int, dst_type: int) -> tuple:
+    """nbxDebugWideLayout: (layout, head) nbxReduceMultiWide would decide for these pointer values
+    (0 elements, 1 packs, 2 realigning; (-1, 0) for bad arguments). Nothing is dereferenced."""
+    d = (ctypes.c_void_p * max(1, len(dsts)))(*[ctypes.c_void_p(int(x)) for x in dsts])
+    s = (ctypes.c_void_p * max(1, len(srcs)))(*[ctypes.c_void_p(int(x)) for x in srcs])
+    head = ctypes.c_size_t(0)
+    layout = load_library().nbxDebugWideLayout(d, len(dsts), s, len(srcs), int(count), int(src_type), int(dst_type),
+                                               ctypes.byref(head))
+    return int(layout), int(head.value)
 
 
 def _reduce_tasks(buckets: Sequence[tuple]) -> tuple:

@@ -10,5 +10,7 @@ void fillWide(WideTable& t) {
   t[9] = makeWideSet<TyBF16>(2);
   t[10] = makeWideSet<TyE4M3>(2);
   t[11] = makeWideSet<TyE5M2>(2);
+  fillWideShift16(t);
+  fillWideShift8(t);
 }
 }  // namespace nbx

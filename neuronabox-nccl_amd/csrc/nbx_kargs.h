@@ -140,6 +140,7 @@ constexpr int wideUnroll(int nSrcs) { return nSrcs >= 4 ? 4 : 1; }
 struct WideSet {
   const void* packs[2][2][kMaxKSrcs];  // [0 = source-type output, 1 = fp32 output][source 0 is an fp32 partial][nSrcs-1]
   const void* elts[2][2];              // element kernels, same first two indices
+  const void* shiftedLds[2][2][kMaxKSrcs];  // realigning kernels (kWideShiftedLds: LDS-DMA staging), indexed as packs
   const void* batchList[2][kMaxKSrcs]; // batched buckets from a work-list table (kWideBatchList), [fp32 output][nSrcs-1]
   int blocksPerCU;                     // at least this many unrolled-tile workgroups per CU
   int eltBytes;

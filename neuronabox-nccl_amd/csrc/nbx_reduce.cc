@@ -293,7 +293,8 @@ enum LaunchFamily {
   kFamSmallPacks = 1, kFamBigPacks = 2, kFamElts = 3, kFamShiftedLds = 4, kFamShifted = 5, kFamWidePacks = 6,
   kFamWideElts = 7,
   kFamBatch = 13, kFamBatchList = 14,   // batched buckets: flags bits kLaunchSegsShift.. = buckets of the launch
-  kFamWideBatchList = 15                // the same for nbxReduceMultiWideBatch (bit 1: fp32 output)
+  kFamWideBatchList = 15,               // the same for nbxReduceMultiWideBatch (bit 1: fp32 output)
+  kFamWideShiftedLds = 16               // wide realigning LDS-DMA (kWideShiftedLds)
 };
 enum LaunchFlag { kLaunchDynamic = 1, kLaunchOut32 = 2, kLaunchPartFirst = 4 };
 struct LaunchLog {
@@ -751,11 +752,42 @@ ncclResult_t reduceMultiImpl(void* const* dsts, int nDsts, const void* const* sr
   return r;
 }
 
+// Layouts of an fp32-accumulating call (wideLayout; nbxDebugWideLayout returns
+// these values).
+enum WideLayout { kWideLayoutElts = 0, kWideLayoutPacks = 1, kWideLayoutShifted = 2 };
+
+// Elements from which a call outside the pack layout takes the realigning
+// kernel (kWideShiftedLds) instead of the element kernel; env
+// NBX_WIDE_SHIFT_MIN_ELTS, nbxDebugSetWideShiftMinElts. The default is the
+// measured crossover (scripts/ab_wide_shift.py, profiles/r9/
+// ab_wide_shift_mi355x.txt): the smallest swept count from which
+// the realigning kernel beats the element kernel for every type, output and
+// 2 / 4 / 8 sources. Below about 512 Ki elements every kernel is launch-bound
+// (3.5-4.3 us) and the 8-source realigning kernel, with its 129 KiB of LDS, has
+// the higher floor (5.2-6.2 us); 2 sources already win from 512 Ki.
+constexpr long long kWideShiftMinEltsDefault = 2097152;
+std::atomic<long long> g_wideShiftMinElts{0};
+long long wideShiftMinElts() {
+  long long v = g_wideShiftMinElts.load(std::memory_order_relaxed);
+  if (v < 1) {
+    long long e = kWideShiftMinEltsDefault;
+    if (const char* s = std::getenv("NBX_WIDE_SHIFT_MIN_ELTS")) {
+      char* end = nullptr;
+      const long long x = std::strtoll(s, &end, 10);
+      if (end != s && x >= 1) e = x;
+    }
+    long long expect = v;
+    g_wideShiftMinElts.compare_exchange_strong(expect, e);
+    v = g_wideShiftMinElts.load();
+  }
+  return v;
+}
+
 // One pass of the fp32-accumulating kernels (nbx_wide.h) over <= kMaxKSrcs
 // sources. partFirst: srcs[0] is the fp32 partial of the earlier passes.
-// fast / head are decided once per call from the caller's pointers (every
+// layout / head are decided once per call from the caller's pointers (every
 // pass of a call folds sources of the same alignment into the same partial).
-ncclResult_t launchWidePass(const WideSet& ws, bool out32, bool partFirst, bool fast, size_t head, void* const* dsts,
+ncclResult_t launchWidePass(const WideSet& ws, bool out32, bool partFirst, int layout, size_t head, void* const* dsts,
                             int nDsts, const void* const* srcs, int nSrcs, size_t count, const nbxDevRedOpFull& op,
                             uint32_t preMask, hipStream_t stream) {
   KArgs a;
@@ -775,7 +807,7 @@ ncclResult_t launchWidePass(const WideSet& ws, bool out32, bool partFirst, bool 
   void* args[] = {&a};
   hipError_t err;
   const int wideFlags = (out32 ? kLaunchOut32 : 0) | (partFirst ? kLaunchPartFirst : 0);
-  if (fast) {
+  if (layout == kWideLayoutPacks) {
     const size_t nPacks = (count - head) / (size_t)(16 / ws.eltBytes);
     a.headElts = (int)head;
     a.nPacks = nPacks;
@@ -796,6 +828,20 @@ ncclResult_t launchWidePass(const WideSet& ws, bool out32, bool partFirst, bool 
                           args, 0, stream);
     logLaunch(kFamWidePacks, nSrcs, unroll, wideFlags | (a.dynCtr != nullptr ? kLaunchDynamic : 0));
     dyn.done(err == hipSuccess);
+  } else if (layout == kWideLayoutShifted) {
+    // 16-byte packs on the destinations' side, the typed sources realigned
+    // through LDS (kWideShiftedLds): the per-step realigning kernel's tile,
+    // workgroups per CU and static schedule
+    const size_t nPacks = (count - head) / (size_t)(16 / ws.eltBytes);
+    a.headElts = (int)head;
+    a.nPacks = nPacks;
+    const int unroll = shiftLdsUnroll(nSrcs);
+    const size_t tile = (size_t)unroll * 64 * kShiftLdsWaves;
+    const size_t tiles = (nPacks + tile - 1) / tile;
+    const size_t grid = cappedGrid(tiles, cus * (size_t)shiftedBlocksPerCU(true, nSrcs));
+    err = hipLaunchKernel(ws.shiftedLds[out32 ? 1 : 0][partFirst ? 1 : 0][nSrcs - 1], dim3((unsigned)grid),
+                          dim3((unsigned)(kShiftLdsWaves * 64)), args, 0, stream);
+    logLaunch(kFamWideShiftedLds, nSrcs, unroll, wideFlags);
   } else {
     const size_t blocks = (count + kBlock - 1) / kBlock;
     const size_t grid = cappedGrid(blocks, cus * (size_t)maxBlocksPerCU(false, nSrcs, /*classic=*/true));
@@ -856,6 +902,25 @@ bool widePackLayout(size_t eb, size_t deb, void* const* dsts, int nDsts, const v
   return fast;
 }
 
+// The layout of a call, decided once from its pointers. Packs: above.
+// Realigning: any other layout whose destinations share one address modulo 16,
+// from wideShiftMinElts() elements; *head is then the elements that bring the
+// destinations to a 16-byte boundary (< 16 / deb), at most count. Everything
+// else — destinations on different alignments, short calls — runs the element
+// kernel (*head = 0). The launch variant has no say.
+int wideLayout(size_t eb, size_t deb, void* const* dsts, int nDsts, const void* const* srcs, int nSrcs, size_t count,
+               size_t* head) {
+  if (widePackLayout(eb, deb, dsts, nDsts, srcs, nSrcs, count, head)) return kWideLayoutPacks;
+  *head = 0;
+  const unsigned dmis = (unsigned)((uintptr_t)dsts[0] & 15u);
+  for (int d = 1; d < nDsts; d++)
+    if (((uintptr_t)dsts[d] & 15u) != dmis) return kWideLayoutElts;
+  if (count < (unsigned long long)wideShiftMinElts()) return kWideLayoutElts;
+  const size_t h = (size_t)((16u - dmis) & 15u) / deb;
+  *head = h > count ? count : h;
+  return kWideLayoutShifted;
+}
+
 ncclResult_t reduceMultiWideImpl(void* const* dsts, int nDsts, const void* const* srcs, int nSrcs, size_t count,
                                  ncclDataType_t srcType, ncclDataType_t dstType, nbxDevRedOpFull op, int nPreOpSrcs,
                                  ncclStream_t stream) {
@@ -875,7 +940,7 @@ ncclResult_t reduceMultiWideImpl(void* const* dsts, int nDsts, const void* const
   hipStream_t strm = (hipStream_t)stream;
 
   size_t head = 0;
-  const bool fast = widePackLayout(eb, deb, dsts, nDsts, srcs, nSrcs, count, &head);
+  const int layout = wideLayout(eb, deb, dsts, nDsts, srcs, nSrcs, count, &head);
 
   auto maskFor = [&](int first, int n, int slot0) {   // sources [first, first + n) sit in slots slot0 ...
     uint32_t m = 0;
@@ -885,14 +950,15 @@ ncclResult_t reduceMultiWideImpl(void* const* dsts, int nDsts, const void* const
     return m;
   };
   if (nSrcs <= kMaxKSrcs)
-    return launchWidePass(ws, out32, false, fast, head, dsts, nDsts, srcs, nSrcs, count, op, maskFor(0, nSrcs, 0),
+    return launchWidePass(ws, out32, false, layout, head, dsts, nDsts, srcs, nSrcs, count, op, maskFor(0, nSrcs, 0),
                           strm);
 
   // > 8 sources: ordered passes of 8 + 7 + 7 ... through an fp32 partial that
   // is never narrowed, so the result is the single fp32 left fold. The
   // partial lives in dsts[0] when the output is fp32 (no source overlaps it),
   // else in stream-ordered scratch (graph-capturable), placed so that its
-  // body behind the head elements is 16-byte aligned like the sources'.
+  // body behind the head elements is 16-byte aligned like the sources' (pack
+  // layout) or the destinations' (realigning layout, which reads it by packs).
   void* scratch = nullptr;
   void* part = dsts[0];
   if (!out32) {
@@ -901,7 +967,7 @@ ncclResult_t reduceMultiWideImpl(void* const* dsts, int nDsts, const void* const
   }
   void* partDst[1] = {part};
   // the partial is fp32 whatever the output: its passes use the fp32-output kernels
-  ncclResult_t r = launchWidePass(ws, true, false, fast, head, partDst, 1, srcs, kMaxKSrcs, count, op,
+  ncclResult_t r = launchWidePass(ws, true, false, layout, head, partDst, 1, srcs, kMaxKSrcs, count, op,
                                   maskFor(0, kMaxKSrcs, 0), strm);
   int next = kMaxKSrcs;
   while (r == ncclSuccess && next < nSrcs) {
@@ -911,7 +977,7 @@ ncclResult_t reduceMultiWideImpl(void* const* dsts, int nDsts, const void* const
     int n = 1;
     while (n < kMaxKSrcs && next < nSrcs) ps[n++] = srcs[next++];
     const bool last = next >= nSrcs;
-    r = launchWidePass(ws, last ? out32 : true, true, fast, head, last ? dsts : partDst, last ? nDsts : 1, ps, n, count,
+    r = launchWidePass(ws, last ? out32 : true, true, layout, head, last ? dsts : partDst, last ? nDsts : 1, ps, n, count,
                        op, maskFor(first, n - 1, 1), strm);
   }
   if (scratch != nullptr && hipFreeAsync(scratch, strm) != hipSuccess && r == ncclSuccess) r = ncclUnhandledCudaError;
@@ -1365,7 +1431,7 @@ ncclResult_t reduceMultiWideBatchImpl(const nbxReduceTask* tasks, int nTasks, nc
     if (t.count == 0) continue;
     size_t head = 0;
     bool single = force == 2 || t.nSrcs > kMaxKSrcs || t.count > kBatchCountMask ||
-                  !widePackLayout(eb, deb, t.dsts, t.nDsts, t.srcs, t.nSrcs, t.count, &head);
+                  wideLayout(eb, deb, t.dsts, t.nDsts, t.srcs, t.nSrcs, t.count, &head) != kWideLayoutPacks;
     if (!single && force == 0 && t.nSrcs > 3)
       single = (t.count - head) / (16 / eb) >= (uint64_t)wideUnroll(t.nSrcs) * kBlock * cus;
     if (single) {
@@ -1511,6 +1577,31 @@ __attribute__((visibility("default"))) int nbxDebugSetDynMinTiles(int tilesPerWo
   const int prev = dynMinTilesPerWG();
   if (tilesPerWorkgroup >= 1) g_dynMinTiles.store(tilesPerWorkgroup);
   return prev;
+}
+
+__attribute__((visibility("default"))) long long nbxDebugSetWideShiftMinElts(long long elts) {
+  const long long prev = wideShiftMinElts();
+  if (elts >= 1) g_wideShiftMinElts.store(elts);
+  return prev;
+}
+
+__attribute__((visibility("default"))) int nbxDebugWideLayout(void* const* dsts, int nDsts, const void* const* srcs,
+                                                              int nSrcs, size_t count, ncclDataType_t srcType,
+                                                              ncclDataType_t dstType, size_t* head) {
+  const int st = (int)srcType, dt = (int)dstType;
+  if (st != ncclFloat16 && st != ncclBfloat16 && st != ncclFloat8e4m3 && st != ncclFloat8e5m2) return -1;
+  if (dt != st && dt != (int)ncclFloat32) return -1;
+  if (nSrcs < 1 || nSrcs > NBX_MAX_SRCS || nDsts < 1 || nDsts > NBX_MAX_DSTS) return -1;
+  if (srcs == nullptr || dsts == nullptr) return -1;
+  const size_t eb = (size_t)typeSize(st), deb = dt != st ? sizeof(float) : eb;
+  for (int s = 0; s < nSrcs; s++)
+    if (srcs[s] == nullptr || ((uintptr_t)srcs[s] % eb) != 0) return -1;
+  for (int d = 0; d < nDsts; d++)
+    if (dsts[d] == nullptr || ((uintptr_t)dsts[d] % deb) != 0) return -1;
+  size_t h = 0;
+  const int layout = wideLayout(eb, deb, dsts, nDsts, srcs, nSrcs, count, &h);
+  if (head != nullptr) *head = h;
+  return layout;
 }
 
 }  // extern "C"

@@ -25,4 +25,7 @@ void fillFp8(KernelTable& t);
 // fp32-accumulating sums: one WideSet per source type (f16, bf16, fp8)
 typedef WideSet WideTable[kNumTypes];
 void fillWide(WideTable& t);
+// their realigning kernels, per element width (called by fillWide)
+void fillWideShift16(WideTable& t);
+void fillWideShift8(WideTable& t);
 }  // namespace nbx

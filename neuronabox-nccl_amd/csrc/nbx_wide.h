@@ -9,16 +9,19 @@
 // is either narrowed once (the type's own narrowing: RNE, fp8 behind
 // satFinite) or stored as fp32.
 //
-// Two kernels per (type, output kind, partial-first):
+// Three kernels per (type, output kind, partial-first):
 //   * kWidePacks<W, NSRC, U, OUT32, PART>: the kReducePacks shape — each lane
 //     issues all NSRC x U 16-byte nt loads of a tile, then folds pack by pack
 //     (8 fp32 accumulators for a 16-bit pack, 16 for an fp8 pack) and stores
 //     one dwordx4 per destination (narrow output) or 2 / 4 of them (fp32
 //     output). Needs every source on one misalignment modulo 16 and every
 //     destination 16-byte aligned after the head elements are peeled.
-//   * kWideElts<W, OUT32, PART>: one element per lane, any alignment. Correct
-//     and slow. The LDS-DMA realigning path of the per-step kernels has no
-//     wide form.
+//   * kWideShiftedLds<W, NSRC, OUT32, PART>: the kReduceShiftedLds shape —
+//     packs on the destinations' side, the typed sources through LDS by
+//     LDS-DMA and realigned on the LDS read. Needs the destinations on one
+//     address modulo 16; taken from NBX_WIDE_SHIFT_MIN_ELTS elements.
+//   * kWideElts<W, OUT32, PART>: one element per lane, any alignment: the
+//     destinations on different alignments, and calls below that threshold.
 // PART: source 0 is the fp32 partial of an earlier pass (more than 8 sources
 // fold in passes of 8 + 7 + 7 ...; the partial is never narrowed, so the
 // result is the single fp32 left fold over all sources).
@@ -277,6 +280,151 @@ __global__ __launch_bounds__(kBlock) void kWideElts(KArgs a) {
     wideElt<W, OUT32, PART>(a, sc, a.nSrcs, i);
 }
 
+// Realigning kernel: kReduceShiftedLds' staging (nbx_kernels.h — the typed
+// sources through LDS by global_load_lds dwordx4 nt, a private two-stage buffer
+// per wave, counted vmcnt between the stages, each output's 16 source bytes
+// read back at its byte offset and funnelled with v_alignbyte) around
+// wideFoldStore at one pack per call. The body is addressed on the destination
+// side: `head` elements bring every destination to a 16-byte boundary, output
+// pack q is one dwordx4 store per destination (source-type output) or kEPP / 4
+// of them (fp32), and the sources sit on any alignment of their own. The fp32
+// partial of a PART pass is 16-byte aligned behind `head` (reduceMultiWideImpl
+// places it so), so it is read straight from global memory with ldPack —
+// before the next tile's DMA is issued, so that the counted wait retires it
+// together with this tile's DMA — and only the NSRC - 1 typed sources are
+// staged. Static schedule only: wave gw takes wave tiles gw, gw + nWaves, ...
+// Memory safety is kReduceShiftedLds': pack indices clamp to the last pack
+// holding a byte of the source's range, and a body of 0 packs has 0 tiles, so
+// no DMA is issued at all.
+template <class W, int NSRC, bool OUT32, bool PART>
+__global__ __launch_bounds__(kShiftLdsWaves * 64) void kWideShiftedLds(KArgs a) {
+  using E = typename W::Elt;
+  constexpr int EPP = W::kEPP, Q = EPP / 4;
+  static_assert(!PART || NSRC >= 2, "a pass that reads a partial folds at least one more source");
+  static_assert(kShiftLdsWaves * 64 == kBlock, "the head and tail elements count on kBlock lanes");
+  constexpr int F = PART ? 1 : 0;   // first staged source
+  constexpr int NST = NSRC - F;     // staged sources
+  constexpr int U = shiftLdsUnroll(NSRC), S = kShiftLdsStages, WV = kShiftLdsWaves;
+  constexpr int P = U * 64 + 1;     // packs per source per stage
+  constexpr uint64_t kTile = (uint64_t)U * 64;
+  __shared__ u32x4 sm[WV][S][NST][P];
+  const float sc = loadWideArg(a);
+  const uint64_t head = (uint64_t)a.headElts;
+  const uint64_t n = a.nPacks;
+  const u32x4* base[NSRC];
+  uint32_t sh[NSRC];
+  uint64_t lim[NSRC];
+#pragma unroll
+  for (int s = F; s < NSRC; s++) {
+    const uintptr_t q = (uintptr_t)a.src[s] + head * sizeof(E);
+    sh[s] = (uint32_t)(q & 15u);
+    base[s] = (const u32x4*)(q - sh[s]);
+    lim[s] = sh[s] ? n : (n ? n - 1 : 0);
+  }
+  const u32x4* partial = (const u32x4*)((const char*)a.src[0] + head * sizeof(float));   // PART only
+  u32x4* dst[kMaxKDsts];
+#pragma unroll
+  for (int d = 0; d < kMaxKDsts; d++) dst[d] = (u32x4*)((char*)a.dst[d] + head * (OUT32 ? sizeof(float) : sizeof(E)));
+  const int nDsts = a.nDsts;
+  const bool pre = a.preMask != 0;   // uniform: the fold is chosen per tile, never per element
+  float mul[NSRC];
+#pragma unroll
+  for (int s = 0; s < NSRC; s++) mul[s] = ((a.preMask >> s) & 1u) ? sc : 1.0f;
+  const int wave = (int)(threadIdx.x >> 6), lane = (int)(threadIdx.x & 63u);
+  const uint64_t nTiles = (n + kTile - 1) / kTile;
+  const uint64_t nWaves = (uint64_t)gridDim.x * WV, gw = (uint64_t)blockIdx.x * WV + (uint64_t)wave;
+  auto issue = [&](uint64_t t, int st) {
+    const uint64_t p0 = t * kTile;
+#pragma unroll
+    for (int s = F; s < NSRC; s++) {
+#pragma unroll
+      for (int u = 0; u < U; u++) {
+        const uint64_t q = p0 + (uint64_t)(u * 64 + lane);
+        __builtin_amdgcn_global_load_lds((const void*)(base[s] + (q < lim[s] ? q : lim[s])),
+                                         (__attribute__((address_space(3))) void*)&sm[wave][st][s - F][u * 64], 16, 0,
+                                         2 /* nt */);
+      }
+      if (lane == 0) {
+        const uint64_t q = p0 + kTile;
+        __builtin_amdgcn_global_load_lds((const void*)(base[s] + (q < lim[s] ? q : lim[s])),
+                                         (__attribute__((address_space(3))) void*)&sm[wave][st][s - F][kTile], 16, 0,
+                                         2);
+      }
+    }
+  };
+  // the fp32 partial of wave tile t (lanes past the body read its last pack)
+  auto loadPart = [&](uint64_t t, u32x4 (&part)[U][Q]) {
+    if constexpr (PART) {
+#pragma unroll
+      for (int u = 0; u < U; u++) {
+        const uint64_t q = t * kTile + (uint64_t)(u * 64 + lane);
+        const uint64_t qc = q < n ? q : n - 1;
+#pragma unroll
+        for (int j = 0; j < Q; j++) part[u][j] = ldPack(partial + qc * Q + j);
+      }
+    }
+  };
+  // fold wave tile t from stage st (its DMA has landed) and store it
+  auto foldTile = [&](uint64_t t, int st, const u32x4 (&part)[U][Q]) {
+#pragma unroll
+    for (int u = 0; u < U; u++) {
+      const uint64_t q = t * kTile + (uint64_t)(u * 64 + lane);
+      if (q < n) {
+        u32x4 part1[1][Q];
+        u32x4 v1[NSRC][1];
+        if constexpr (PART) {
+#pragma unroll
+          for (int j = 0; j < Q; j++) part1[0][j] = part[u][j];
+        }
+#pragma unroll
+        for (int s = F; s < NSRC; s++) {
+          const uint32_t o = (uint32_t)(u * 64 + lane) * 16u + sh[s];
+          const uint32_t* w = (const uint32_t*)&sm[wave][st][s - F][0] + (o >> 2);
+          const uint32_t b = o & 3u;
+          const uint32_t w0 = w[0], w1 = w[1], w2 = w[2], w3 = w[3], w4 = b ? w[4] : 0u;
+          v1[s][0] = u32x4{__builtin_amdgcn_alignbyte(w1, w0, b), __builtin_amdgcn_alignbyte(w2, w1, b),
+                           __builtin_amdgcn_alignbyte(w3, w2, b), __builtin_amdgcn_alignbyte(w4, w3, b)};
+        }
+        if (pre) wideFoldStore<W, NSRC, 1, OUT32, PART, true>(part1, v1, mul, dst, nDsts, q);
+        else wideFoldStore<W, NSRC, 1, OUT32, PART, false>(part1, v1, mul, dst, nDsts, q);
+      }
+    }
+    // this stage's LDS reads have returned before a later iteration refills it
+    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+  };
+#pragma unroll
+  for (int k = 0; k < S - 1; k++) {
+    const uint64_t t = gw + (uint64_t)k * nWaves;
+    if (t < nTiles) issue(t, k);
+  }
+  int st = 0;
+  for (uint64_t t = gw; t < nTiles; t += nWaves) {
+    u32x4 part[U][Q];
+    loadPart(t, part);
+    if (t + (uint64_t)(S - 1) * nWaves < nTiles) {
+      issue(t + (uint64_t)(S - 1) * nWaves, (st + S - 1) % S);
+      // everything but the newer tiles' DMA (NST x (U + 1) instructions each)
+      // has landed: this tile's DMA and its partial; stores counted in vmcnt
+      // only make the wait stricter
+      asm volatile("s_waitcnt vmcnt(%0)" ::"n"((S - 1) * NST * (U + 1)) : "memory");
+    } else {
+      asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    }
+    foldTile(t, st, part);
+    st = st + 1 == S ? 0 : st + 1;
+  }
+
+  // head (before the destinations' 16-B boundary) and tail elements
+  if (blockIdx.x == gridDim.x - 1) {
+    const int h = a.headElts;
+    const uint64_t tailStart = head + n * EPP;
+    const int tail = (int)(a.nElts - tailStart);
+    const int th = (int)threadIdx.x;
+    if (th < h) wideElt<W, OUT32, PART>(a, sc, NSRC, (uint64_t)th);
+    else if (th < h + tail) wideElt<W, OUT32, PART>(a, sc, NSRC, tailStart + (uint64_t)(th - h));
+  }
+}
+
 // ---------------------------------------------------------------------------
 // Batched buckets (nbxReduceMultiWideBatch): kReduceBatchList's scheduler
 // (nbx_kernels.h — records from the table in BatchListArgs::recs, running tile
@@ -403,6 +551,28 @@ template <class W, bool OUT32, int... I>
 void fillWideBatch(WideSet& ws, std::integer_sequence<int, I...>) {
   const void* list[] = {(const void*)&kWideBatchList<W, I + 1, OUT32>...};
   for (int i = 0; i < kMaxKSrcs; i++) ws.batchList[OUT32 ? 1 : 0][i] = list[i];
+}
+
+template <class W, bool OUT32, int... I, int... J>
+void fillWideShifted(WideSet& ws, std::integer_sequence<int, I...>, std::integer_sequence<int, J...>) {
+  const void* first[] = {(const void*)&kWideShiftedLds<W, I + 1, OUT32, false>...};
+  const void* later[] = {nullptr, (const void*)&kWideShiftedLds<W, J + 2, OUT32, true>...};
+  for (int i = 0; i < kMaxKSrcs; i++) {
+    ws.shiftedLds[OUT32 ? 1 : 0][0][i] = first[i];
+    ws.shiftedLds[OUT32 ? 1 : 0][1][i] = later[i];
+  }
+}
+
+// The realigning kernels of one source type, added to its set by a unit of
+// their own (inst_wide_shift*.hip: 30 kernels per type, compiled in parallel
+// with the pack kernels).
+template <class Ty>
+void addWideShifted(WideSet& ws) {
+  using W = WideTy<Ty>;
+  constexpr std::make_integer_sequence<int, kMaxKSrcs> all{};
+  constexpr std::make_integer_sequence<int, kMaxKSrcs - 1> fromTwo{};
+  fillWideShifted<W, false>(ws, all, fromTwo);
+  fillWideShifted<W, true>(ws, all, fromTwo);
 }
 
 template <class Ty>
