@@ -70,6 +70,27 @@ int nbxDebugCommProtoMask(ncclComm_t comm);
  * count; -1 for a bad handle or a communicator without a multi-rank transport. */
 int nbxDebugCommSettings(ncclComm_t comm, int64_t* out, int nOut);
 
+/* The Simple transport's protocol state of a communicator (its own, or a
+ * clique rank's in-process transport's), read once the device is idle: the
+ * call synchronises the device, then copies this rank's 4 * nRanks * grid
+ * counter words (what its workgroups carry from call to call: 0 RS sent, 1 RS
+ * received, 2 AG sent, 3 AG received, per peer) and its own 4 * nRanks * grid
+ * flag words (what its peers post into: 0 RS ready, 1 RS credit, 2 AG ready,
+ * 3 AG credit, per poster) to the host; grid is out[4] of
+ * nbxDebugCommSettings. Index of both arrays: (kind * nRanks + who) * grid + g
+ * for peer `who` and workgroup g (nbx_simple.h simpleFlag). *prefetch: whether
+ * the direct schedule pushes the next round before it folds this one
+ * (NBX_SIMPLE_PREFETCH). Returns the words per array; -1 for a bad handle or a
+ * NULL pointer, a communicator without that transport or still being created,
+ * nWords (the capacity of each array) too small, or a HIP error. Read-only
+ * host code: no kernel, nothing on any data path changes. The peers' posts
+ * into the flag words are only final once every rank's device is idle: a test
+ * synchronises every rank and meets on the host before it reads. A
+ * communicator that reported an asynchronous error is still read (its state
+ * is the evidence); the caller must not race the call with ncclCommDestroy or
+ * ncclCommAbort of the same communicator. Test hook. */
+int nbxDebugSimpleState(ncclComm_t comm, uint64_t* counters, uint64_t* flags, size_t nWords, int* prefetch);
+
 /* Config D's xGMI transport alone, on a multi-process
  * communicator: an AllReduce-shaped call of the direct Simple schedule (forced
  * for any size and NCCL_ALGO) that moves every byte an AllReduce of `count`

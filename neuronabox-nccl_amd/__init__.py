@@ -229,6 +229,10 @@ def load_library(path: Optional[str] = None) -> ctypes.CDLL:
                                        ctypes.c_int, ctypes.c_size_t, ctypes.c_int, ctypes.c_int,
                                        ctypes.POINTER(ctypes.c_size_t)]
     lib.nbxDebugWideLayout.restype = ctypes.c_int
+    # test hook of the Simple transport: counters and flag words of a communicator at rest
+    lib.nbxDebugSimpleState.argtypes = [ctypes.c_void_p, ctypes.POINTER(ctypes.c_uint64),
+                                        ctypes.POINTER(ctypes.c_uint64), ctypes.c_size_t, ctypes.POINTER(ctypes.c_int)]
+    lib.nbxDebugSimpleState.restype = ctypes.c_int
     if path is None:
         _lib = lib
     return lib
@@ -379,6 +383,21 @@ def launch_log(max_records: int = LAUNCH_LOG_CAP) -> tuple:
     total = load_library().nbxDebugLaunchLog(buf, int(max_records))
     k = min(total, max_records, LAUNCH_LOG_CAP)
     return total, [tuple(buf[4 * i:4 * i + 4]) for i in range(k)]
+
+
+def simple_state(comm, n_words: int) -> Optional[tuple]:
+    """nbxDebugSimpleState: (counters, flags, prefetch) of a communicator's Simple transport once
+    the device is idle — two lists of 4 * nRanks * grid words, index (kind * nRanks + who) * grid + g —
+    or None where the hook returns -1 (bad handle, no such transport, n_words too small).
+    `comm` is a Communicator or a raw handle (None: the NULL handle)."""
+    handle = comm.handle if isinstance(comm, Communicator) else ctypes.c_void_p(comm)
+    counters = (ctypes.c_uint64 * max(1, n_words))()
+    flags = (ctypes.c_uint64 * max(1, n_words))()
+    prefetch = ctypes.c_int(-1)
+    k = load_library().nbxDebugSimpleState(handle, counters, flags, int(n_words), ctypes.byref(prefetch))
+    if k < 0:
+        return None
+    return list(counters[:k]), list(flags[:k]), int(prefetch.value)
 
 
 def reduce_multi_raw(dsts: Sequence[int], srcs: Sequence[int], count: int, dtype: int, op: DevRedOpFull,

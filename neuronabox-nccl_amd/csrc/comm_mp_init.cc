@@ -197,6 +197,30 @@ long ncclEnvMapped(const char* nbxName, const char* ncclName, long dflt, long nu
 // tries), then freed. The same runtime condition also makes a successful
 // export name the wrong memory now and then (mpConnect, which verifies every
 // mapping and re-exports what is wrong).
+//
+// Exported buffers are never given back to the runtime (the pool below).
+// A rank that destroys its communicator used to hipFree what its peers still
+// had mapped (a peer closes its mappings at its own destroy, and nothing makes
+// the ranks meet there), and every later communicator exported fresh
+// allocations at addresses whose earlier allocation had been exported and
+// freed — the one condition under which the probe above saw refused and wrong
+// exports (0 of 19,200 with exported buffers never freed). So freeSyncMem
+// keeps an exported buffer, with the IPC handle it was exported under, and
+// allocSyncMem hands it to the next communicator of this process that asks
+// for the same size on the same device; the caller clears it as it clears a
+// new allocation. A buffer whose export mpConnect found wrong is kept but not
+// handed out again. The pool holds at most what the process's communicators
+// held at their peak, per distinct size (sizes are whole 2 MiB pages).
+struct ExportedBuf {
+  void* p;
+  size_t bytes;
+  int device;
+  hipIpcMemHandle_t handle;
+  bool inUse, retired;
+};
+std::mutex g_exportedMu;
+std::vector<ExportedBuf> g_exported;
+
 hipError_t allocSyncMem(void** p, size_t bytes, hipIpcMemHandle_t* handle /* nullptr: in-process only */) {
   static const bool coarse = [] {
     const char* v = std::getenv("NBX_SYNC_MEM");
@@ -204,6 +228,18 @@ hipError_t allocSyncMem(void** p, size_t bytes, hipIpcMemHandle_t* handle /* nul
   }();
   const size_t page = (size_t)2 << 20;
   bytes = (bytes + page - 1) / page * page;
+  int device = -1;
+  if (handle != nullptr) {
+    if (hipGetDevice(&device) != hipSuccess) return hipErrorInvalidDevice;
+    std::lock_guard<std::mutex> g(g_exportedMu);
+    for (ExportedBuf& b : g_exported)
+      if (!b.inUse && !b.retired && b.bytes == bytes && b.device == device) {
+        b.inUse = true;
+        *p = b.p;
+        *handle = b.handle;
+        return hipSuccess;
+      }
+  }
   std::vector<void*> refused;
   hipError_t e = hipSuccess;
   for (int attempt = 0; attempt < 4; attempt++) {
@@ -219,7 +255,28 @@ hipError_t allocSyncMem(void** p, size_t bytes, hipIpcMemHandle_t* handle /* nul
     *p = nullptr;
   }
   for (void* q : refused) (void)hipFree(q);
+  if (e == hipSuccess && handle != nullptr) {
+    std::lock_guard<std::mutex> g(g_exportedMu);
+    g_exported.push_back(ExportedBuf{*p, bytes, device, *handle, true, false});
+  }
   return e;
+}
+
+// Gives a buffer of allocSyncMem back: an exported one to the pool (`wrong`:
+// its export named other memory, it is never handed out again), any other to
+// the runtime.
+void freeSyncMem(void* p, bool wrong = false) {
+  if (p == nullptr) return;
+  {
+    std::lock_guard<std::mutex> g(g_exportedMu);
+    for (ExportedBuf& b : g_exported)
+      if (b.p == p) {
+        b.inUse = false;
+        b.retired = b.retired || wrong;
+        return;
+      }
+  }
+  (void)hipFree(p);
 }
 
 // A device spin gave up (host error word set): name the wait, the peer, the
@@ -551,7 +608,7 @@ ncclResult_t mpConnect(ncclComm* c, const std::vector<MpInitInfo>& all) {
       }
     }
   }
-  for (void* q : retired) (void)hipFree(q);
+  for (void* q : retired) freeSyncMem(q, /*wrong=*/true);
   NCCLCHECK(res);
   // the device tables of peer buffers (own entry: own buffer)
   std::vector<uint64_t*> llTable(n), l128Table(n, nullptr), flagTable(n);
@@ -685,10 +742,13 @@ void mpFreeState(MpState* mp, int device) {
   DevGuard g(device);
   (void)hipDeviceSynchronize();
   for (void* p : mp->peerMaps) (void)hipIpcCloseMemHandle(p);
-  for (void* p : {(void*)mp->peerStageDev, (void*)mp->peerSFlagsDev, (void*)mp->scounters, (void*)mp->sflags,
-                  (void*)mp->stage, (void*)mp->peerL128Dev, (void*)mp->l128, (void*)mp->peerLLDev, (void*)mp->ll,
-                  (void*)mp->llState, (void*)mp->orderMem, (void*)mp->probeSink})
+  for (void* p : {(void*)mp->peerStageDev, (void*)mp->peerSFlagsDev, (void*)mp->scounters, (void*)mp->peerL128Dev,
+                  (void*)mp->peerLLDev, (void*)mp->llState, (void*)mp->orderMem, (void*)mp->probeSink})
     if (p) (void)hipFree(p);
+  // the connection buffers: what peers may still have mapped stays allocated (allocSyncMem)
+  // (after an abort or a device wait that gave up a peer's kernel may still store into them: kept, not reused)
+  const bool failed = mp->hostWords != nullptr && (mp->hostWords[0] != 0 || mp->hostWords[1] != 0);
+  for (void* p : {(void*)mp->sflags, (void*)mp->stage, (void*)mp->l128, (void*)mp->ll}) freeSyncMem(p, failed);
   for (hipEvent_t e : mp->groupEvents) (void)hipEventDestroy(e);
   nbx::bootstrapClose(mp->bs);
   delete mp;
@@ -902,6 +962,29 @@ NBX_EXPORT int nbxDebugCommSettings(ncclComm_t comm, int64_t* out, int nOut) {
   int k = 0;
   for (; k < nOut && k < 11; k++) out[k] = v[k];
   return k;
+}
+
+// The Simple transport's protocol state after the device went idle: this
+// rank's counter words and its own flag words (the ones its peers post into),
+// 4 * nRanks * simpleGrid each, index (kind * nRanks + who) * simpleGrid + g
+// (nbx_simple.h simpleFlag). Read-only: a device synchronisation and two
+// copies to the host. Returns the words per array, -1 for a bad handle, a
+// communicator without that transport, nWords too small or a HIP error.
+NBX_EXPORT int nbxDebugSimpleState(ncclComm_t comm, uint64_t* counters, uint64_t* flags, size_t nWords,
+                                   int* prefetch) {
+  if (comm == nullptr || comm->magic != kCommMagic || counters == nullptr || flags == nullptr || prefetch == nullptr)
+    return -1;
+  if (comm->asyncError.load() == ncclInProgress) return -1;   // still being created
+  const MpState* mp = mpOf(comm);
+  if (mp == nullptr || mp->scounters == nullptr || mp->sflags == nullptr || mp->simpleGrid < 1) return -1;
+  const size_t words = 4 * (size_t)comm->nRanks * (size_t)mp->simpleGrid;
+  if (nWords < words || words > (size_t)INT32_MAX) return -1;
+  DevGuard g(comm->device);
+  if (hipDeviceSynchronize() != hipSuccess) return -1;
+  if (hipMemcpy(counters, mp->scounters, words * sizeof(uint64_t), hipMemcpyDeviceToHost) != hipSuccess) return -1;
+  if (hipMemcpy(flags, mp->sflags, words * sizeof(uint64_t), hipMemcpyDeviceToHost) != hipSuccess) return -1;
+  *prefetch = mp->simplePrefetch;
+  return (int)words;
 }
 
 NBX_EXPORT int nbxDebugChooseProto(int protoMask, int twoShotKind, uint64_t slotBytes, uint64_t blockBytes, int nRanks,
