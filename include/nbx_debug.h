@@ -183,7 +183,7 @@ int nbxDebugWideLayout(void* const* dsts, int nDsts, const void* const* srcs, in
 
 /* Per-stream counters allocated so far on `device` by the dynamic schedules
  * (which: 0 = big-tile reduce's tile counters, 1 = realigning kernel's class
- * counters); keyed by stream handle (nbx_reduce.cc). -1 bad device. */
+ * counters); keyed by stream handle (nbx_policy.cc). -1 bad device. */
 int nbxDebugDynStreamSlots(int device, int which);
 
 /* Holds `stream` with a one-wave kernel until nbxDebugReleaseStream(hold) or
@@ -226,7 +226,7 @@ int nbxDebugReleaseStream(int hold);
  * communicator creation launches collectives too: on the creating thread, or
  * on the background thread of a non-blocking ncclCommInitRankConfig — reset
  * the log after creation.
- * Batched launches of nbxReduceMultiBatch (nbx_reduce.cc BatchPacker::flush /
+ * Batched launches of nbxReduceMultiBatch (nbx_reduce_batch.cc BatchPacker::flush /
  * launchBatchList), one record per kernel launched, after the launch
  * succeeded — family: 13 kernel-argument batch (kReduceBatch), 14 work-list
  * batch (kReduceBatchList). nSrcs: the launch's source count. unroll: 1.
@@ -238,7 +238,7 @@ int nbxDebugReleaseStream(int hold);
  * order; then, per source count ascending, that count's work-list launches
  * followed by its kernel-argument launches (the buckets no free table slot
  * was left for; all of them with work lists off or for a small set).
- * Batched launches of nbxReduceMultiWideBatch (nbx_reduce.cc
+ * Batched launches of nbxReduceMultiWideBatch (nbx_reduce_batch.cc
  * launchBatchList), one record per kernel launched, after the launch
  * succeeded — family: 15 wide work-list batch (kWideBatchList). nSrcs: the
  * launch's source count. unroll: 1. flags: bit 1 fp32 output, bits 8.. the

@@ -67,7 +67,7 @@ ncclResult_t mpLaunchLL(ncclComm* comm, const MpCall& c, MpProto proto, const Mp
   la.order = mpOrderArgs(mp);
   la.gridCap = proto == kMpLL ? mp->llGridCap : mp->l128GridCap;
   // launch record (nbx_debug.h): the kernel family, the checking instantiation
-  // (planSig != 0 picks it in nbx_reduce.cc), the group's segments
+  // (planSig != 0 picks it in nbx_coll_launch.cc), the group's segments
   auto launched = [&](ncclResult_t r, int family) {
     if (r == ncclSuccess)
       nbx::logCollLaunch(family, n, 1, (la.planSig != 0 ? nbx::kLaunchChecked : 0) |

@@ -15,7 +15,7 @@ struct KArgs;
 // until done(), which advances the base by the launch's tile count if the
 // launch went out. begin() returns false (static grid stride) while the
 // stream is being captured, for hipStreamPerThread, or with
-// NBX_DYNAMIC_TILES=0 (nbx_reduce.cc).
+// NBX_DYNAMIC_TILES=0 (nbx_policy.cc).
 class DynLaunch {
  public:
   bool begin(int dev, hipStream_t st, uint64_t nTiles, KArgs& a);

@@ -1,5 +1,5 @@
 // nbx_registry.h — kernel table shared by the per-type instantiation units
-// (inst_*.hip, compiled in parallel) and the host launcher (nbx_reduce.cc).
+// (inst_*.hip, compiled in parallel) and the host launchers (nbx_launch.h).
 // Replaces the generated ncclDevFuncTable / ncclDevFuncId of the reference
 // (/root/reference/src/device/generate.py:125-149, src/include/device.h:412-459):
 // one KernelSet per (datatype, device op); signed integers share the

@@ -1,6 +1,6 @@
 // nbx_tiles.h — tile scheduling shared by the reduce kernels and the stream
 // ceiling kernels (device code; the host side is nbx::DynLaunch,
-// nbx_internal.h / nbx_reduce.cc).
+// nbx_internal.h / nbx_policy.cc).
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>

@@ -288,7 +288,7 @@ __global__ __launch_bounds__(kBlock) void kWideElts(KArgs a) {
 // side: `head` elements bring every destination to a 16-byte boundary, output
 // pack q is one dwordx4 store per destination (source-type output) or kEPP / 4
 // of them (fp32), and the sources sit on any alignment of their own. The fp32
-// partial of a PART pass is 16-byte aligned behind `head` (reduceMultiWideImpl
+// partial of a PART pass is 16-byte aligned behind `head` (nbxReduceMultiWide
 // places it so), so it is read straight from global memory with ldPack —
 // before the next tile's DMA is issued, so that the counted wait retires it
 // together with this tile's DMA — and only the NSRC - 1 typed sources are

@@ -106,8 +106,8 @@ def claims(eb):
 
 def packer_geometry(start, count, eb):
     """(head, packs, tiles, tail) of a bucket whose pointers lie start * eb
-    bytes past a 16-byte boundary: BatchPacker::add's arithmetic (nbx_reduce.cc;
-    launchBatchList repeats it)."""
+    bytes past a 16-byte boundary: bucketTiles' arithmetic (nbx_reduce_batch.cc;
+    BatchPacker::add and launchBatchList call it)."""
     epp = 16 // eb
     mis = (start * eb) % 16
     head = (16 - mis) // eb if mis else 0
