@@ -77,6 +77,7 @@ so its calls alternate too (uses 0, 7, 14), but the first call alone already
 fills both slots; the ring's Reduce is a chain over the whole message, two
 rounds of 64 KiB slices, so each of its calls begins on slot 0.
 """
+import copy
 from collections import namedtuple
 
 import numpy as np
@@ -246,6 +247,22 @@ def run_model(n, cfg, calls, grid=GRID, slice_bytes=SLICE, order="rr", seed=0):
         outputs.append([None if x is None else x.view(t) for x in recvs])
     starts.append([c.copy() for c in comm.counters])
     return ModelRun(comm, starts, outputs)
+
+
+def run_model_group(run, n, cfg, grouped, grid=GRID, slice_bytes=SLICE):
+    """The grouped launch on the model (tests/simple_model.py run_group, cut by
+    mp_diag.simple_group_geometry), going on from a copy of `run`'s end state:
+    what every rank's nbxDebugSimpleState must return after the group."""
+    comm = copy.deepcopy(run.comm)
+    first = grouped[0]
+    assert all((c.kind, c.dtype, c.op) == (first.kind, first.dtype, first.op) for c in grouped)
+    geom = mp_diag.simple_group_geometry([(c.kind, c.count) for c in grouped], first.eb, n, grid, slice_bytes,
+                                         ring=cfg.ring)
+    sends = [[rank_input(c, n, r).view(np.uint8) for r in range(n)] for c in grouped]
+    recvs = [[np.full(c.count * c.eb, 0xA5, np.uint8) for _r in range(n)] for c in grouped]
+    sm.run_group(comm, first.kind, geom, sends, recvs, first.eb, _model_fold(first), ring=cfg.ring,
+                 prefetch=bool(cfg.prefetch))
+    return ModelRun(comm, [run.starts[-1]], [[x.view(np_type(first)) for x in seg] for seg in recvs]), geom
 
 
 def idx(n, grid, kind, who, g):

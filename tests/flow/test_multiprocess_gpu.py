@@ -147,11 +147,13 @@ def _reference(oracle, which, n, grid, slice_bytes):
         if key not in folded:
             folded[key] = [cases.expected(oracle, c, [cases.rank_input(c, n, r) for r in range(n)], n, cfg.ring)
                            for c in calls + grouped]
-        ref[cfg.name] = (folded[key], cases.run_model(n, cfg, calls, grid, slice_bytes))
+        model = cases.run_model(n, cfg, calls, grid, slice_bytes)
+        ref[cfg.name] = (folded[key], model, cases.run_model_group(model, n, cfg, grouped, grid, slice_bytes)
+                         if grouped else None)
     return ref
 
 
-def _check_outputs(cfg, n, calls, first_grouped, exp, res, model, grid, slice_bytes, failures):
+def _check_outputs(cfg, n, calls, first_grouped, exp, res, model, gmodel, grid, slice_bytes, failures):
     checked = 0
     for ci, call in enumerate(calls):
         part = "grouped " if ci >= first_grouped else ""
@@ -174,9 +176,17 @@ def _check_outputs(cfg, n, calls, first_grouped, exp, res, model, grid, slice_by
             base = r * e.size if call.kind == "rs" else 0
             cand = {f"raw_input_rank{j}": cases.rank_input(call, n, j)[base:base + e.size] for j in range(n)}
             cand["guard_fill"] = np.full(e.nbytes, 0xA5, np.uint8).view(e.dtype)
+            if ci >= first_grouped:   # a segment of the grouped launch: the launch's own cut
+                d = mp_diag.describe_mismatch(got, e, None, base, cand)
+                bad = np.flatnonzero(got != e)
+                loc = gmodel[1].locate(ci - first_grouped, bad + base)
+                failures.append(f"{ctx}: {mp_diag.format_mismatch(d)}; first at {loc[0].tolist()} last at "
+                                f"{loc[-1].tolist()} (segment, block, round, workgroup, slice offset) of the grouped "
+                                f"launch, sliceOff {gmodel[1].slice_off}")
+                continue
             d = mp_diag.describe_mismatch(got, e, cases.geometry(call, n, grid, slice_bytes, cfg.ring), base, cand)
             where = ""
-            if d.get("cells") and ci < first_grouped:   # the model has no groups
+            if d.get("cells"):
                 c = d["cells"][0]
                 where = "; top cell " + cases.slot_report(call, cfg, n, r, (c["block"], c["round"], c["workgroup"]),
                                                           model.starts[ci])
@@ -202,9 +212,10 @@ def _run_and_check(nbx, oracle, which, n, monkeypatch, grid_guess, slice_bytes):
     for cfg, _env, calls, grouped in plan:
         s = res[0][cfg.name]["settings"]
         grid = s["simpleGrid"]
-        exp, model = ref[cfg.name]
+        exp, model, gmodel = ref[cfg.name]
         if grid != grid_guess:   # the first-use test takes the grid from the communicator
             model = cases.run_model(n, cfg, calls, grid, slice_bytes)
+            gmodel = cases.run_model_group(model, n, cfg, grouped, grid, slice_bytes) if grouped else None
         for r in range(n):
             got = res[r][cfg.name]
             # the settings the communicator was asked for took effect, on every rank
@@ -229,7 +240,8 @@ def _run_and_check(nbx, oracle, which, n, monkeypatch, grid_guess, slice_bytes):
                     failures.append(f"{cfg.name} rank {r}: grouped launch record {total} {recs}, expected {want}")
         if which == "matrix":
             assert grid == cases.GRID, (cfg.name, s)
-        outputs += _check_outputs(cfg, n, calls + grouped, len(calls), exp, res, model, grid, slice_bytes, failures)
+        outputs += _check_outputs(cfg, n, calls + grouped, len(calls), exp, res, model, gmodel, grid, slice_bytes,
+                                  failures)
         # the state against the model, then the invariants that need no model (again after the group)
         states = [res[r][cfg.name]["state"][:2] for r in range(n)]
         failures += [f"{cfg.name} state vs model: {x}" for x in cases.check_model(states, model.comm, n, grid)]
@@ -237,6 +249,9 @@ def _run_and_check(nbx, oracle, which, n, monkeypatch, grid_guess, slice_bytes):
         state_words += sum(len(a) + len(b) for a, b in states)
         if grouped:
             after = [res[r][cfg.name]["group_state"][:2] for r in range(n)]
+            # the grouped launch against the grouped model, word for word: the slot uses it should have consumed
+            failures += [f"{cfg.name} state after the grouped launch vs model: {x}"
+                         for x in cases.check_model(after, gmodel[0].comm, n, grid)]
             failures += [f"{cfg.name} after the grouped launch: {x}" for x in cases.check_pairs(after, n, grid)]
             if all(np.array_equal(a[0], b[0]) for a, b in zip(states, after)):
                 failures.append(f"{cfg.name}: the grouped launch left every counter where it was")
@@ -262,8 +277,9 @@ def test_simple_flow_matrix(nbx, oracle, n, monkeypatch):
     ran as one launch of four segments; every output equals the oracle in the
     schedule's order with its guard bytes intact; every rank's counters and
     flag words equal the model's, word for word; the pairwise invariants hold
-    at rest, and again after the grouped launch (which the model does not
-    have). Every rank and call is checked before the test fails; a wrong
+    at rest; after the grouped launch the counters and flag words equal the
+    grouped model's (simple_model.run_group), word for word, and the pairwise
+    invariants hold again. Every rank and call is checked before the test fails; a wrong
     output is reported with its (block, round, workgroup) cells and the slot
     and use of the top one."""
     outputs, words = _run_and_check(nbx, oracle, "matrix", n, monkeypatch, cases.GRID, cases.SLICE)

@@ -8,6 +8,11 @@ nbx_simple.h simpleSlice), and what the wrong values look like — zero, a
 peer's raw input, the fold with one source missing, the previous call's
 output, ... (any candidate arrays the caller passes).
 
+The grouped form has its mirror here too: group_runs restates runMpGroup's cut
+of a group into launches (with the reason of every cut and the launch records
+it leaves), ll_group_units and simple_group_geometry the segment tables of one
+grouped launch (tests/test_group_segments_cpu.py, tests/groups/).
+
 Pure numpy: the CPU suite tests the mapping with synthetic mismatches
 (tests/test_mp_diag_cpu.py); the GPU tests and the stress scripts call
 `assert_same` in place of a bare `np.array_equal` assert.
@@ -77,6 +82,219 @@ def simple_geometry(kind: str, count: int, eb: int, n: int, simple_grid: int, sl
     sl = min(sl, slice_bytes)
     rounds = -(-block_bytes // (grid * sl)) if block_bytes else 0
     return SimpleGeometry(kind, count, eb, n, max(block, 1), total, grid, max(sl // eb, 1), rounds)
+
+
+@dataclass
+class SimpleGroupGeometry:
+    """How one grouped Simple launch cuts its segments (comm_mp_launch.cc
+    mpLaunchSimple, nc > 1; nbx_simple.h simpleSlice)."""
+    kind: str
+    eb: int
+    n: int
+    block_elts: list    # per segment
+    totals: list        # per segment: elements of the send-side message
+    slices: list        # per segment: virtual slices of a block
+    slice_off: list     # per segment: its first virtual slice of every block
+    grid: int
+    slice_bytes: int
+    n_rounds: int
+
+    @property
+    def slice_elts(self) -> int:
+        return max(self.slice_bytes // self.eb, 1)
+
+    def segment_of(self, v: int) -> int:
+        """simpleSlice's lookup: the last segment starting at or before virtual slice v."""
+        s = 0
+        for q in range(1, len(self.slice_off)):
+            if v >= self.slice_off[q]:
+                s = q
+        return s
+
+    def span(self, b: int, k: int, g: int) -> tuple:
+        """(segment, first element, elements) that workgroup g moves of block b in round k."""
+        v = k * self.grid + g
+        s = self.segment_of(v)
+        blk, tot = self.block_elts[s], self.totals[s]
+        lo = min(b * blk, tot)
+        hi = tot if tot - lo < blk else lo + blk
+        s0 = (v - self.slice_off[s]) * self.slice_elts
+        return s, lo + s0, (0 if s0 >= hi - lo else min(hi - lo - s0, self.slice_elts))
+
+    def locate(self, seg: int, idx) -> np.ndarray:
+        """Rows (segment, block, round, workgroup, element offset in the slice)
+        for send-side element indices idx of segment seg."""
+        idx = np.asarray(idx, dtype=np.int64)
+        blk = max(self.block_elts[seg], 1)
+        b = idx // blk
+        off = idx - b * blk
+        v = off // self.slice_elts + self.slice_off[seg]
+        return np.stack([np.full_like(b, seg), b, v // self.grid, v % self.grid,
+                         off - (v - self.slice_off[seg]) * self.slice_elts], axis=1)
+
+    def shifted(self, q: int, d: int) -> "SimpleGroupGeometry":
+        """A wrong cut, for the model only: the segment before q counted d
+        slices off, so segment q and every later one start d slices away from
+        where they should and the rounds follow the wrong total."""
+        off = [o + (d if s >= q else 0) for s, o in enumerate(self.slice_off)]
+        rounds = -(-(sum(self.slices) + d) // self.grid)
+        return SimpleGroupGeometry(self.kind, self.eb, self.n, self.block_elts, self.totals, self.slices, off,
+                                   self.grid, self.slice_bytes, rounds)
+
+
+def simple_group_geometry(run, eb: int, n: int, grid_max: int, slice_bytes: int,
+                          ring: bool = False) -> SimpleGroupGeometry:
+    """The host's cut of one grouped Simple launch. run: [(kind, count)] of its
+    segments (one kind). Grid, slice and rounds come from the SUM of the
+    segments' block bytes; segment s owns virtual slices [slice_off[s],
+    slice_off[s] + slices[s]) of every block."""
+    kind = run[0][0]
+    blocks, totals = [], []
+    for k, count in run:
+        assert k == kind
+        if kind == "rs":
+            blk, tot = count, count * n
+        elif kind == "red" and ring:
+            blk, tot = count, count
+        else:
+            lo, hi = block_range(count, eb, n, 0)
+            blk, tot = hi - lo, count
+        blocks.append(blk)
+        totals.append(tot)
+    seg_bytes = [min(b, t) * eb for b, t in zip(blocks, totals)]
+    block_bytes = sum(seg_bytes)
+    grid = max(1, min(-(-block_bytes // MIN_SLICE_BYTES), grid_max))
+    sl = min(((-(-block_bytes // grid)) + 15) & ~15, slice_bytes) if block_bytes else slice_bytes
+    slices = [-(-sb // sl) for sb in seg_bytes]
+    offs = [sum(slices[:s]) for s in range(len(slices))]
+    return SimpleGroupGeometry(kind, eb, n, blocks, totals, slices, offs, grid, sl, -(-sum(slices) // grid))
+
+
+def ll_group_units(run, eb: int, unit: int) -> tuple:
+    """(packOff of every segment, total units) of one grouped LL (unit 8: packs)
+    or LL128 one-shot (unit 48: lines) launch; run: the segments' counts
+    (comm_mp_launch.cc mpLaunchLL)."""
+    offs, units = [], 0
+    for count in run:
+        offs.append(units)
+        units += -(-count * eb // unit)
+    return offs, units
+
+
+# ---------------------------------------------------------------------------
+# The group cut (comm_mp_launch.cc runMpGroup)
+
+@dataclass
+class GroupCall:
+    """One queued call as runMpGroup sees it. send / recv: byte addresses (any
+    common origin; recv None where a Reduce non-root passes NULL). op: anything
+    that compares equal exactly where the device op and its scalar do."""
+    kind: str            # "ar", "rs", "red"
+    dtype: int
+    eb: int
+    op: object
+    count: int
+    send: int
+    recv: object
+    root: int = 0
+    user_premul: bool = False
+
+
+@dataclass
+class GroupPlan:
+    runs: list       # [(first call, one past the last)]
+    reasons: list    # why run k ended where it did, for every boundary (len(runs) - 1)
+    protos: list     # the protocol of each run
+    records: list    # the launch records the group leaves: (family, n, unroll, nSegs << 8)
+
+
+GROUP_MAX_SEGS = 16   # nbx_ll_args.h kLLMaxSegs, kSimpleMaxSegs
+CUT_REASONS = ("op", "proto", "max_segs", "capacity", "zero_count", "reduce", "user_premul", "conflict", "batch_off")
+FAMILY_OF_PROTO = {"LL": 8, "LL128": 9, "LL128x2": 10, "Simple": 11}   # include/nbx_debug.h; the ring: 12
+
+
+def _call_spans(c: GroupCall, n: int) -> list:
+    send_bytes = (c.count * n if c.kind == "rs" else c.count) * c.eb
+    out = [(c.send, c.send + send_bytes, False)]
+    if c.recv is not None:
+        out.append((c.recv, c.recv + c.count * c.eb, True))
+    return out
+
+
+def _spans_conflict(a: list, b: list) -> bool:
+    return any((xw or yw) and xlo < yhi and ylo < xhi for xlo, xhi, xw in a for ylo, yhi, yw in b)
+
+
+def group_runs(calls, n: int, settings: dict, proto_mask: int = 7, ring: bool = False,
+               oneshot_max: int = 256 << 10) -> GroupPlan:
+    """runMpGroup's cut of a group's queued calls into launches, restated: the
+    runs, the reason every run but the last ended where it did (the first
+    condition of the library's loop that stopped it, CUT_REASONS), and the
+    launch records the group must leave. settings: comm_settings' dictionary
+    (llMax, l128Max, groupBatch)."""
+    def proto(c):
+        return proto_of(c.kind, c.count, c.eb, n, settings, proto_mask, oneshot_max) if c.count > 0 else "Simple"
+
+    def units(c, p):
+        return -(-c.count * c.eb // (8 if p == "LL" else L128_DATA_BYTES))
+
+    def same_op(a, b):
+        return a.kind == b.kind and a.dtype == b.dtype and a.op == b.op and (a.kind != "red" or a.root == b.root)
+
+    cap = {"LL": settings.get("llMax", 64 << 10) // 8, "LL128": l128_slot_lines(settings.get("l128Max", 1 << 20))}
+    batch = bool(settings.get("groupBatch", 1))
+    runs, reasons, protos, records = [], [], [], []
+    i = 0
+    while i < len(calls):
+        j, head = i + 1, calls[i]
+        p = proto(head)
+        why = None
+        if not batch:
+            why = "batch_off"
+        elif head.kind == "red":
+            why = "reduce"
+        elif head.user_premul:
+            why = "user_premul"
+        elif p == "LL128x2":
+            why = "proto"   # the two-shot kernel is never grouped
+        else:
+            used = 0 if p == "Simple" else units(head, p)
+            spans = _call_spans(head, n)
+            while j < len(calls):
+                c = calls[j]
+                if j - i >= GROUP_MAX_SEGS:
+                    why = "max_segs"
+                elif c.count == 0:
+                    why = "zero_count"
+                elif c.user_premul:
+                    why = "user_premul"
+                elif c.kind == "red":
+                    why = "reduce"
+                elif not same_op(head, c):
+                    why = "op"
+                elif proto(c) != p:
+                    why = "proto"
+                elif p != "Simple" and used + units(c, p) > cap[p]:
+                    why = "capacity"
+                elif _spans_conflict(spans, _call_spans(c, n)):
+                    why = "conflict"
+                else:
+                    spans += _call_spans(c, n)
+                    used += 0 if p == "Simple" else units(c, p)
+                    j += 1
+                    continue
+                break
+            if j - i == 1 and head.count == 0:
+                why = "zero_count"
+        runs.append((i, j))
+        protos.append(p)
+        if j < len(calls):
+            reasons.append(why)
+        if j - i > 1 or head.count > 0:
+            fam = 12 if p == "Simple" and ring else FAMILY_OF_PROTO[p]
+            records.append((fam, n, 0 if p == "Simple" else 1, ((j - i) << 8) if j - i > 1 else 0))
+        i = j
+    return GroupPlan(runs, reasons, protos, records)
 
 
 def _runs(idx: np.ndarray, limit: int = 6) -> list:

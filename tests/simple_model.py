@@ -6,7 +6,9 @@ step for step — the same slice arithmetic (simpleSlice), staging layout
 (simpleStage), flag words, per-pair counters, credits and the next-round
 prefetch — yielding whenever the kernel would spin on a flag. A scheduler
 interleaves them (round robin or seeded random order) until every one has
-finished, or reports a deadlock if none can move. Data moves through numpy
+finished, or reports a deadlock if none can move. run_call is one collective;
+run_group one grouped launch over a segment table, each workgroup looking its
+virtual slice up as simpleSlice does. Data moves through numpy
 byte arrays, folds through the oracle's ordered left fold. Test
 infrastructure only (nothing in the product imports it)."""
 from __future__ import annotations
@@ -64,7 +66,7 @@ def _slice(block, total, sl_elts, grid, b, k, g):
     return lo + s0, (0 if s0 >= hi - lo else min(hi - lo - s0, sl_elts))
 
 
-def _wg(comm, me, g, kind, ring, shape, send, recv, eb, fold, root, prefetch, stats):
+def _wg(comm, me, g, kind, ring, shape, send, recv, eb, fold, root, prefetch, stats, segs=None):
     """One workgroup of one rank's kernel (a generator; yields while spinning)."""
     n, slots = comm.n, comm.slots
     block, total, grid, sl, rounds = shape
@@ -92,6 +94,25 @@ def _wg(comm, me, g, kind, ring, shape, send, recv, eb, fold, root, prefetch, st
     def elts(buf, off, c):
         return buf[off * eb:(off + c) * eb]
 
+    def span(b, k):
+        """simpleSlice: (send, recv, block size, first element, elements) of what
+        this workgroup moves of block b in round k — of the launch's one message,
+        or of the segment that owns virtual slice k * grid + g (segs: (send, recv,
+        blockElts, total, sliceOff) per segment, sliceOff ascending)."""
+        if segs is None:
+            off, c = _slice(block, total, sle, grid, b, k, g)
+            return send, recv, block, off, c
+        v = k * grid + g
+        sg = segs[0]
+        for cand in segs[1:]:
+            if v >= cand[4]:
+                sg = cand
+        s_send, s_recv, blk, tot, first = sg
+        lo = min(b * blk, tot)
+        hi = tot if tot - lo < blk else lo + blk
+        s0 = (v - first) * sle
+        return s_send, s_recv, blk, lo + s0, (0 if s0 >= hi - lo else min(hi - lo - s0, sle))
+
     if not ring:
         ar, red = kind == "ar", kind == "red"
         store_local = not red or me == root
@@ -107,9 +128,9 @@ def _wg(comm, me, g, kind, ring, shape, send, recv, eb, fold, root, prefetch, st
                     yield from wait(RS_CREDIT, t, cnt[RS_SENT][t] + 1 - slots)
             for q in range(1, n):
                 j = (me + q) % n
-                off, c = _slice(block, total, sle, grid, j, k, g)
+                s_send, _r, _b, off, c = span(j, k)
                 if c:
-                    stage(j, 0, cnt[RS_SENT][j] % slots, me, c * eb)[:] = elts(send, off, c)
+                    stage(j, 0, cnt[RS_SENT][j] % slots, me, c * eb)[:] = elts(s_send, off, c)
             for t in range(n):
                 if t != me:
                     cnt[RS_SENT][t] += 1
@@ -121,15 +142,15 @@ def _wg(comm, me, g, kind, ring, shape, send, recv, eb, fold, root, prefetch, st
                     yield from wait(RS_READY, t, cnt[RS_RECV][t] + 1)
                     if push_target(t) and cnt[AG_SENT][t] + 1 > slots:
                         yield from wait(AG_CREDIT, t, cnt[AG_SENT][t] + 1 - slots)
-            off, c = _slice(block, total, sle, grid, me, k, g)
+            s_send, s_recv, blk, off, c = span(me, k)
             if c:
                 srcs = []
                 for q in range(n):
                     j = (first + q) % n
-                    srcs.append(elts(send, off, c) if j == me else stage(me, 0, cnt[RS_RECV][j] % slots, j, c * eb))
+                    srcs.append(elts(s_send, off, c) if j == me else stage(me, 0, cnt[RS_RECV][j] % slots, j, c * eb))
                 res = fold(srcs)
                 if store_local:
-                    elts(recv, off - me * block if kind == "rs" else off, c)[:] = res
+                    elts(s_recv, off - me * blk if kind == "rs" else off, c)[:] = res
                 for q in range(1, n):
                     p = (me + q) % n
                     if push_target(p):
@@ -148,9 +169,9 @@ def _wg(comm, me, g, kind, ring, shape, send, recv, eb, fold, root, prefetch, st
                     yield from wait(AG_READY, t, cnt[AG_RECV][t] + 1)
             for q in range(1, n):
                 j = (me + q) % n
-                off, c = _slice(block, total, sle, grid, j, k, g)
+                _s, s_recv, _b, off, c = span(j, k)
                 if c:
-                    elts(recv, off, c)[:] = stage(me, 1, cnt[AG_RECV][j] % slots, j, c * eb)
+                    elts(s_recv, off, c)[:] = stage(me, 1, cnt[AG_RECV][j] % slots, j, c * eb)
             for t in range(n):
                 if t != me:
                     cnt[AG_RECV][t] += 1
@@ -197,36 +218,36 @@ def _wg(comm, me, g, kind, ring, shape, send, recv, eb, fold, root, prefetch, st
         for k in range(rounds):
             if red:
                 pos = (me - root - 1 + 2 * n) % n
-                off, c = _slice(block, total, sle, grid, 0, k, g)
+                s_send, s_recv, _b, off, c = span(0, k)
                 push = pos < n - 1
                 yield from hop_wait(-1 if pos == 0 else 0, push, False)
                 if c:
                     if pos == 0:
-                        out = elts(send, off, c)
+                        out = elts(s_send, off, c)
                     else:
                         recv_part = stage(me, 0, cnt[RS_RECV][left] % slots, left, c * eb)
-                        out = fold([elts(send, off, c), recv_part], pre_mask=3 if pos == 1 else 1, post=not push)
+                        out = fold([elts(s_send, off, c), recv_part], pre_mask=3 if pos == 1 else 1, post=not push)
                     if push:
                         stage(right, 0, cnt[RS_SENT][right] % slots, me, c * eb)[:] = out
                     else:
-                        elts(recv, off, c)[:] = out
+                        elts(s_recv, off, c)[:] = out
                 hop_post(-1 if pos == 0 else 0, push, False)
                 continue
-            off, c = _slice(block, total, sle, grid, left, k, g)
+            s_send, _r, _b, off, c = span(left, k)
             yield from hop_wait(-1, True, False)
             if c:
-                stage(right, 0, cnt[RS_SENT][right] % slots, me, c * eb)[:] = elts(send, off, c)
+                stage(right, 0, cnt[RS_SENT][right] % slots, me, c * eb)[:] = elts(s_send, off, c)
             hop_post(-1, True, False)
             for st in range(n - 1):
                 ch = (me + 2 * n - 2 - st) % n
                 last = st == n - 2
-                off, c = _slice(block, total, sle, grid, ch, k, g)
+                s_send, s_recv, blk, off, c = span(ch, k)
                 yield from hop_wait(0, not last, last and ar)
                 if c:
                     recv_part = stage(me, 0, cnt[RS_RECV][left] % slots, left, c * eb)
-                    out = fold([elts(send, off, c), recv_part], pre_mask=3 if st == 0 else 1, post=last)
+                    out = fold([elts(s_send, off, c), recv_part], pre_mask=3 if st == 0 else 1, post=last)
                     if last:
-                        elts(recv, off if ar else off - me * block, c)[:] = out
+                        elts(s_recv, off if ar else off - me * blk, c)[:] = out
                         if ar:
                             stage(right, 1, cnt[AG_SENT][right] % slots, me, c * eb)[:] = out
                     else:
@@ -237,11 +258,11 @@ def _wg(comm, me, g, kind, ring, shape, send, recv, eb, fold, root, prefetch, st
             for st in range(n - 1):
                 ch = (me + 2 * n - 1 - st) % n
                 fwd = st < n - 2
-                off, c = _slice(block, total, sle, grid, ch, k, g)
+                _s, s_recv, _b, off, c = span(ch, k)
                 yield from hop_wait(1, False, fwd)
                 if c:
                     part = stage(me, 1, cnt[AG_RECV][left] % slots, left, c * eb)
-                    elts(recv, off, c)[:] = part
+                    elts(s_recv, off, c)[:] = part
                     if fwd:
                         stage(right, 1, cnt[AG_SENT][right] % slots, me, c * eb)[:] = part
                 hop_post(1, False, fwd)
@@ -264,6 +285,34 @@ def run_call(comm, kind, sends, recvs, count, eb, fold, root=0, ring=False, pref
         for g in range(shape[2]):
             gens.append(_wg(comm, r, g, kind, ring, shape, sends[r], recvs[r], eb,
                             fold, root, prefetch, stats))
+    return _schedule(gens, stats, order, seed, max_steps)
+
+
+def run_group(comm, kind, geom, sends, recvs, eb, fold, ring=False, prefetch=True, order="rr", seed=0,
+              max_steps=10_000_000):
+    """Run one grouped launch (comm_mp_launch.cc mpLaunchSimple with nc > 1) on
+    every rank: one kernel over the segments' blocks back to back, each
+    workgroup looking its virtual slice up in the segment table as simpleSlice
+    does. geom: mp_diag.simple_group_geometry of the launch (grid, slice,
+    rounds, per-segment blockElts / total / sliceOff); sends[s][rank] and
+    recvs[s][rank] are segment s's uint8 arrays. A group holds AllReduces or
+    ReduceScatters only (a Reduce is never grouped). Returns the scheduler
+    statistics."""
+    assert kind in ("ar", "rs") and len(sends) == len(recvs) == len(geom.slice_off)
+    stats = {"spins": 0, "steps": 0, "moves": 0}
+    if sum(geom.slices) == 0:
+        return stats
+    shape = (None, None, geom.grid, geom.slice_bytes, geom.n_rounds)
+    gens = []
+    for r in range(comm.n):
+        segs = [(sends[s][r], recvs[s][r], geom.block_elts[s], geom.totals[s], geom.slice_off[s])
+                for s in range(len(sends))]
+        for g in range(geom.grid):
+            gens.append(_wg(comm, r, g, kind, ring, shape, None, None, eb, fold, 0, prefetch, stats, segs))
+    return _schedule(gens, stats, order, seed, max_steps)
+
+
+def _schedule(gens, stats, order, seed, max_steps):
     rng = random.Random(seed)
     live = list(gens)
     stuck = 0

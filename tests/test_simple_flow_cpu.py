@@ -32,6 +32,38 @@ def _states(run, n):
     return [(run.comm.counters[r].copy(), run.comm.flags[r].copy()) for r in range(n)]
 
 
+@pytest.mark.parametrize("cfg", [cases.CONFIGS[0], cases.CONFIGS[5], cases.CONFIGS[8], cases.CONFIGS[11]],
+                         ids=lambda c: c.name)
+@pytest.mark.parametrize("n", cases.NS)
+def test_grouped_launch_on_the_model(oracle, n, cfg):
+    """The four AllReduces of the GPU test's grouped launch as ONE launch on the
+    model, going on from the state a sequence left: every segment exact against
+    the oracle, the invariants hold, and every cell advanced by the launch's
+    rounds: segment 0 is 3 (S + 1) whole slices, the others one 16-byte slice
+    more, 12 (S + 1) + 3 virtual slices in 4 (S + 1) + 1 rounds of 3 — more
+    than the S slots, and every segment boundary but the first inside a round."""
+    before = cases.run_model(n, cfg, cases.sequence(n, cfg)[:6])
+    grouped = cases.group_calls(n, cfg)
+    run, geom = cases.run_model_group(before, n, cfg, grouped)
+    full = 3 * (cfg.slots + 1)
+    assert geom.slices == [full, full + 1, full + 1, full + 1] and (geom.grid, geom.slice_bytes) == (cases.GRID, cases.SLICE)
+    assert geom.n_rounds == 4 * (cfg.slots + 1) + 1 > cfg.slots
+    assert [o % cases.GRID for o in geom.slice_off] == [0, 0, 1, 2]
+    for s, call in enumerate(grouped):
+        exp = cases.expected(oracle, call, [cases.rank_input(call, n, r) for r in range(n)], n, cfg.ring)
+        for r in range(n):
+            assert np.array_equal(run.outputs[s][r], exp[r]), (s, r)
+    assert cases.check_pairs(_states(run, n), n, cases.GRID) == []
+    hops = (n - 1) if cfg.ring else 1
+    for r in range(n):
+        d = run.comm.counters[r].astype(np.int64) - before.comm.counters[r].astype(np.int64)
+        to = (r + 1) % n
+        for g in range(cases.GRID):
+            assert d[cases.idx(n, cases.GRID, sm.RS_SENT, to, g)] == geom.n_rounds * hops
+            assert d[cases.idx(n, cases.GRID, sm.AG_SENT, to, g)] == geom.n_rounds * hops
+    assert all(np.array_equal(a, b) for a, b in zip(before.comm.counters, before.starts[-1]))   # a copy went on
+
+
 def _uses(run, n, grid, ci, kind):
     """{(a, b, g): uses} of counter `kind` (a's count toward b) during call ci."""
     out = {}
