@@ -1,5 +1,10 @@
-"""The in-process clique's in-kernel LL / LL128 transport (cliqueInitTransport,
-comm_clique.cc) as a GPU test: scripts/clique_stress.py forces it on for ranks
+"""The randomized half of the tests of the in-process clique's in-kernel
+transport (cliqueInitTransport, comm_clique.cc); tests/clique/ is the
+deterministic half: every (type, op) with edge-value inputs through each
+protocol kernel, one case per routing rule, groups and the hand-over between
+the two paths, each with the launch record of the path it took.
+
+Here scripts/clique_stress.py forces the transport on for ranks
 sharing the one GPU of the test box (NBX_CLIQUE_LL=1, each rank on its own
 streams and hardware queues, both set in that fresh process before HIP loads),
 runs random plans of AllReduce / ReduceScatter / Reduce across LL, LL128 one-
