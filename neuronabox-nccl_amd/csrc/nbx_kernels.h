@@ -27,12 +27,14 @@
 
 namespace nbx {
 
-
-
-
 // Device-resident scalar: read the element's bytes while the kernel runs
 // (reference: common.h:100-119 / onerank.cu:32-42 dereference by alignment;
 // reading exactly sizeof(T) yields the same scalar bits).
+// The batch kernels spell this and acquirePeerData out over their own argument
+// structs: called with the struct by reference or with its fields, these two
+// functions compile every batch kernel whose functor reads the scalar
+// differently, and written as one conditional expression (the batch kernels'
+// form) loadArg costs the 64-bit types a memory instruction (profiles/r12).
 template <class Fn>
 __device__ __forceinline__ uint64_t loadArg(const KArgs& a) {
   if (a.argPtr != nullptr) return (uint64_t) * (const typename Fn::Elt*)a.argPtr;
@@ -199,6 +201,14 @@ __global__ __launch_bounds__(kBlock) void kReduceElts(KArgs a) {
 // Memory safety: a 16-B aligned pack never crosses a page, and every pack
 // loaded holds at least one byte of the source range (pack indices are
 // clamped to the last one), so no load can touch an unmapped page.
+
+// A source pointer as its 16-B aligned-down base and its byte offset past it
+// (both kernels here and kWideShiftedLds, nbx_wide.h).
+__device__ __forceinline__ void alignDown16(uintptr_t q, const u32x4*& base, uint32_t& sh) {
+  sh = (uint32_t)(q & 15u);
+  base = (const u32x4*)(q - sh);
+}
+
 __device__ __forceinline__ u32x4 funnel16(const u32x4& lo, const u32x4& hi, uint32_t m) {
   const uint32_t b = m & 3u;   // byte shift inside a dword (0: plain dword select)
   const uint32_t w[8] = {lo.x, lo.y, lo.z, lo.w, hi.x, hi.y, hi.z, hi.w};
@@ -236,9 +246,7 @@ __global__ __launch_bounds__(kBlock) void kReduceShifted(KArgs a) {
   uint32_t sh[kMaxKSrcs];
 #pragma unroll
   for (int s = 0; s < kMaxKSrcs; s++) {
-    const uintptr_t q = (uintptr_t)a.src[s < nSrcs ? s : 0] + headBytes;
-    sh[s] = (uint32_t)(q & 15u);
-    base[s] = (const u32x4*)(q - sh[s]);
+    alignDown16((uintptr_t)a.src[s < nSrcs ? s : 0] + headBytes, base[s], sh[s]);
   }
   u32x4* dst[kMaxKDsts];
 #pragma unroll
@@ -284,6 +292,18 @@ __global__ __launch_bounds__(kBlock) void kReduceShifted(KArgs a) {
   }
 }
 
+// Output pack o of a wave tile from one source's row of an LDS stage
+// (kReduceShiftedLds below and kWideShiftedLds, nbx_wide.h): its 16 bytes sit
+// at byte offset 16 o + sh of the row — five dwords and a byte funnel shift.
+__device__ __forceinline__ u32x4 stageRead(const u32x4* row, uint32_t sh, uint32_t o) {
+  const uint32_t off = o * 16u + sh;
+  const uint32_t* w = (const uint32_t*)row + (off >> 2);
+  const uint32_t b = off & 3u;
+  const uint32_t w0 = w[0], w1 = w[1], w2 = w[2], w3 = w[3], w4 = b ? w[4] : 0u;
+  return u32x4{__builtin_amdgcn_alignbyte(w1, w0, b), __builtin_amdgcn_alignbyte(w2, w1, b),
+               __builtin_amdgcn_alignbyte(w3, w2, b), __builtin_amdgcn_alignbyte(w4, w3, b)};
+}
+
 // Per-source-count realigning kernel: the sources go through LDS by LDS-DMA.
 // A wave's tile is U x 64 output packs (destination side, 16-B aligned); it
 // needs packs [p0, p0 + U*64] of each source's aligned-down base: U full
@@ -317,9 +337,7 @@ __global__ __launch_bounds__(kShiftLdsWaves * 64) void kReduceShiftedLds(KArgs a
   uint64_t lim[NSRC];
 #pragma unroll
   for (int s = 0; s < NSRC; s++) {
-    const uintptr_t q = (uintptr_t)a.src[s] + headBytes;
-    sh[s] = (uint32_t)(q & 15u);
-    base[s] = (const u32x4*)(q - sh[s]);
+    alignDown16((uintptr_t)a.src[s] + headBytes, base[s], sh[s]);
     lim[s] = sh[s] ? n : n - 1;
   }
   u32x4* dst[kMaxKDsts];
@@ -358,12 +376,7 @@ __global__ __launch_bounds__(kShiftLdsWaves * 64) void kReduceShiftedLds(KArgs a
         u32x4 acc;
 #pragma unroll
         for (int s = 0; s < NSRC; s++) {
-          const uint32_t o = (uint32_t)(u * 64 + lane) * 16u + sh[s];
-          const uint32_t* w = (const uint32_t*)&sm[wave][st][s][0] + (o >> 2);
-          const uint32_t b = o & 3u;
-          const uint32_t w0 = w[0], w1 = w[1], w2 = w[2], w3 = w[3], w4 = b ? w[4] : 0u;
-          u32x4 x = {__builtin_amdgcn_alignbyte(w1, w0, b), __builtin_amdgcn_alignbyte(w2, w1, b),
-                     __builtin_amdgcn_alignbyte(w3, w2, b), __builtin_amdgcn_alignbyte(w4, w3, b)};
+          u32x4 x = stageRead(&sm[wave][st][s][0], sh[s], (uint32_t)(u * 64 + lane));
           if constexpr (Fn::kHasPre) if ((preMask >> s) & 1u) x = fn.prePack(x);
           if (s == 0) acc = x;
           else acc = fn.redPack(acc, x);
@@ -633,8 +646,6 @@ namespace nbx {
 // ---------------------------------------------------------------------------
 // Launch table for one functor.
 
-
-
 // Two tile shapes per source count. BIG keeps ~32 dwordx4 loads (512 B) in
 // flight per lane and runs one 256-thread workgroup per CU (the best 8:1
 // shape measured: 6.1-6.2 TB/s); SMALL (U = 1) gives small buckets enough
@@ -643,12 +654,6 @@ template <int NSRC, int CAP>
 constexpr int bigUnroll() {
   constexpr int u = NSRC >= 5 ? 4 : (NSRC >= 3 ? 8 : 16);
   return u < CAP ? u : CAP;
-}
-
-// per-source-count realigning kernels (LDS-DMA staging)
-template <class Fn, int NSRC>
-inline const void* shiftedNFor() {
-  return (const void*)&kReduceShiftedLds<Fn, NSRC>;
 }
 
 template <class Fn, int... I>
@@ -668,7 +673,7 @@ KernelSet makeKernelSetImpl(std::integer_sequence<int, I...>) {
   }
   ks.elts = (const void*)&kReduceElts<Fn>;
   ks.shifted = (const void*)&kReduceShifted<Fn>;
-  const void* sn[] = {shiftedNFor<Fn, I + 1>()...};
+  const void* sn[] = {(const void*)&kReduceShiftedLds<Fn, I + 1>...};   // per-source-count realigning kernels
   for (int i = 0; i < kMaxKSrcs; i++) ks.shiftedN[i] = sn[i];
   ks.ll = (const void*)&kLLColl<Fn, false>;
   ks.ll128 = (const void*)&kLL128Coll<Fn, false>;

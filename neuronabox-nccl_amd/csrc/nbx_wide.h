@@ -91,9 +91,8 @@ struct WideTy<TyE5M2> : WideTyF8<TyE5M2> {};
 
 // The PreMulSum scalar is an fp32 value: the low 32 bits of scalarArg, or a
 // float in device memory read while the kernel runs.
-__device__ __forceinline__ float loadWideArg(const KArgs& a) {
-  if (a.argPtr != nullptr) return *(const float*)a.argPtr;
-  return __uint_as_float((uint32_t)a.arg);
+__device__ __forceinline__ float loadWideArg(const void* argPtr, uint64_t arg) {
+  return argPtr != nullptr ? *(const float*)argPtr : __uint_as_float((uint32_t)arg);
 }
 
 // One element, any source count <= kMaxKSrcs (uniform guards, as reduceElt).
@@ -218,7 +217,7 @@ __global__ __launch_bounds__(kBlock) void kWidePacks(KArgs a) {
   using E = typename W::Elt;
   constexpr int EPP = W::kEPP, Q = EPP / 4;
   static_assert(!PART || NSRC >= 2, "a pass that reads a partial folds at least one more source");
-  const float sc = loadWideArg(a);
+  const float sc = loadWideArg(a.argPtr, a.arg);
   const uint64_t head = (uint64_t)a.headElts;
   const u32x4* src[NSRC];
 #pragma unroll
@@ -274,7 +273,7 @@ __global__ __launch_bounds__(kBlock) void kWidePacks(KArgs a) {
 // that is not 16-byte aligned behind the head.
 template <class W, bool OUT32, bool PART>
 __global__ __launch_bounds__(kBlock) void kWideElts(KArgs a) {
-  const float sc = loadWideArg(a);
+  const float sc = loadWideArg(a.argPtr, a.arg);
   const uint64_t stride = (uint64_t)gridDim.x * kBlock;
   for (uint64_t i = (uint64_t)blockIdx.x * kBlock + threadIdx.x; i < a.nElts; i += stride)
     wideElt<W, OUT32, PART>(a, sc, a.nSrcs, i);
@@ -308,7 +307,7 @@ __global__ __launch_bounds__(kShiftLdsWaves * 64) void kWideShiftedLds(KArgs a) 
   constexpr int P = U * 64 + 1;     // packs per source per stage
   constexpr uint64_t kTile = (uint64_t)U * 64;
   __shared__ u32x4 sm[WV][S][NST][P];
-  const float sc = loadWideArg(a);
+  const float sc = loadWideArg(a.argPtr, a.arg);
   const uint64_t head = (uint64_t)a.headElts;
   const uint64_t n = a.nPacks;
   const u32x4* base[NSRC];
@@ -316,9 +315,7 @@ __global__ __launch_bounds__(kShiftLdsWaves * 64) void kWideShiftedLds(KArgs a) 
   uint64_t lim[NSRC];
 #pragma unroll
   for (int s = F; s < NSRC; s++) {
-    const uintptr_t q = (uintptr_t)a.src[s] + head * sizeof(E);
-    sh[s] = (uint32_t)(q & 15u);
-    base[s] = (const u32x4*)(q - sh[s]);
+    alignDown16((uintptr_t)a.src[s] + head * sizeof(E), base[s], sh[s]);
     lim[s] = sh[s] ? n : (n ? n - 1 : 0);
   }
   const u32x4* partial = (const u32x4*)((const char*)a.src[0] + head * sizeof(float));   // PART only
@@ -378,12 +375,7 @@ __global__ __launch_bounds__(kShiftLdsWaves * 64) void kWideShiftedLds(KArgs a) 
         }
 #pragma unroll
         for (int s = F; s < NSRC; s++) {
-          const uint32_t o = (uint32_t)(u * 64 + lane) * 16u + sh[s];
-          const uint32_t* w = (const uint32_t*)&sm[wave][st][s - F][0] + (o >> 2);
-          const uint32_t b = o & 3u;
-          const uint32_t w0 = w[0], w1 = w[1], w2 = w[2], w3 = w[3], w4 = b ? w[4] : 0u;
-          v1[s][0] = u32x4{__builtin_amdgcn_alignbyte(w1, w0, b), __builtin_amdgcn_alignbyte(w2, w1, b),
-                           __builtin_amdgcn_alignbyte(w3, w2, b), __builtin_amdgcn_alignbyte(w4, w3, b)};
+          v1[s][0] = stageRead(&sm[wave][st][s - F][0], sh[s], (uint32_t)(u * 64 + lane));
         }
         if (pre) wideFoldStore<W, NSRC, 1, OUT32, PART, true>(part1, v1, mul, dst, nDsts, q);
         else wideFoldStore<W, NSRC, 1, OUT32, PART, false>(part1, v1, mul, dst, nDsts, q);
@@ -461,7 +453,7 @@ template <class W, int NSRC, bool OUT32>
 __global__ __launch_bounds__(kBlock) void kWideBatchList(BatchListArgs a) {
   using E = typename W::Elt;
   constexpr int EPP = W::kEPP, Q = EPP / 4;
-  const float sc = a.argPtr != nullptr ? *(const float*)a.argPtr : __uint_as_float((uint32_t)a.arg);
+  const float sc = loadWideArg(a.argPtr, a.arg);
   const uint32_t preMask = a.preMask;
   const bool pre = preMask != 0;   // uniform per launch: the fold is never chosen per element
   float mul[NSRC];
