@@ -70,6 +70,20 @@ int nbxDebugCommProtoMask(ncclComm_t comm);
  * count; -1 for a bad handle or a communicator without a multi-rank transport. */
 int nbxDebugCommSettings(ncclComm_t comm, int64_t* out, int nOut);
 
+/* The settings a transport of nRanks ranks would be created with under the
+ * current environment, with no communicator and no GPU (comm_mp_settings.cc
+ * mpSettings): the smallest GPU has minCus CUs, at most maxShare ranks share a
+ * GPU, the ranks span several GPUs (multiGpu = 1) or not; minCTAs / maxCTAs as
+ * ncclConfig_t holds them (NCCL_CONFIG_UNDEF_INT: unset), checkPointers the
+ * communicator's NCCL_CHECK_POINTERS. out[0..10] as nbxDebugCommSettings
+ * ([8], re-exports, is 0), [11] protocol mask (as nbxDebugGatedProtoMask),
+ * [12] ring schedule (NCCL_ALGO=Ring), [13] LL128 one-shot max bytes, [14] LL
+ * lines per slot, [15] LL128 lines per slot. Writes min(nOut, 16) values and
+ * returns that count; -1 for a NULL out, nRanks outside 2..64, minCus or
+ * maxShare below 1. */
+int nbxDebugTransportSettings(int nRanks, int minCus, int maxShare, int multiGpu, int minCTAs, int maxCTAs,
+                              int checkPointers, int64_t* out, int nOut);
+
 /* The Simple transport's protocol state of a communicator (its own, or a
  * clique rank's in-process transport's), read once the device is idle: the
  * call synchronises the device, then copies this rank's 4 * nRanks * grid

@@ -372,38 +372,16 @@ ncclResult_t cliqueInitTransport(Clique* cl) {
   for (int r = 0; r < n; r++) {
     DevGuard g(cl->devs[r]);
     MpState* mp = new MpState();
-    cl->comms[r]->lt = mp;
-    NCCLCHECK(mpAllocLL(mp, n, /*ipc=*/false, cl->comms[r]));
-    mp->multiGpu = distinct;
-    mp->protoMask = protoGateAcrossGpus(mp->protoMask, mp->multiGpu, std::getenv("NCCL_PROTO"));
-    mp->ring = algoRingFromEnv();
-    mpTransportSettings(mp, minCus, maxShare, cl->comms[r]);   // co-resident grids, as mpInit
-    if (simple) NCCLCHECK(mpAllocSimple(mp, n, /*ipc=*/false));
+    ncclComm* comm = cl->comms[r];
+    comm->lt = mp;
+    // co-resident grids, as mpInit
+    mpSettings(mp, n, minCus, maxShare, /*multiGpu=*/distinct, comm->minCTAs, comm->maxCTAs, comm->checkPointers);
+    NCCLCHECK(mpAlloc(mp, n, /*ipc=*/false, simple, comm));
     mp->extDone = cl->evDone;
-  }
-  std::vector<uint64_t*> llTable(n), l128Table(n), flagTable(n);
-  std::vector<char*> stageTable(n);
-  for (int r = 0; r < n; r++) {
-    llTable[r] = cl->comms[r]->lt->ll;
-    l128Table[r] = cl->comms[r]->lt->l128;
-    stageTable[r] = cl->comms[r]->lt->stage;
-    flagTable[r] = cl->comms[r]->lt->sflags;
   }
   for (int r = 0; r < n; r++) {
     DevGuard g(cl->devs[r]);
-    MpState* mp = cl->comms[r]->lt;
-    HIPCHECK(hipMalloc((void**)&mp->peerLLDev, n * sizeof(uint64_t*)));
-    HIPCHECK(hipMemcpy(mp->peerLLDev, llTable.data(), n * sizeof(uint64_t*), hipMemcpyHostToDevice));
-    if (mp->l128) {
-      HIPCHECK(hipMalloc((void**)&mp->peerL128Dev, n * sizeof(uint64_t*)));
-      HIPCHECK(hipMemcpy(mp->peerL128Dev, l128Table.data(), n * sizeof(uint64_t*), hipMemcpyHostToDevice));
-    }
-    if (simple) {
-      HIPCHECK(hipMalloc((void**)&mp->peerStageDev, n * sizeof(char*)));
-      HIPCHECK(hipMemcpy(mp->peerStageDev, stageTable.data(), n * sizeof(char*), hipMemcpyHostToDevice));
-      HIPCHECK(hipMalloc((void**)&mp->peerSFlagsDev, n * sizeof(uint64_t*)));
-      HIPCHECK(hipMemcpy(mp->peerSFlagsDev, flagTable.data(), n * sizeof(uint64_t*), hipMemcpyHostToDevice));
-    }
+    NCCLCHECK(connUploadTables(cl->comms[r]->lt, n, [&](int j, int t) { return cl->comms[j]->lt->conn[t].own; }));
     HIPCHECK(hipDeviceSynchronize());   // zeroed and uploaded before any peer's first kernel
   }
   cl->ll = true;
@@ -453,16 +431,7 @@ ncclResult_t cliqueRunLL(Clique* c, const std::vector<std::vector<PendingColl>>&
 // fold-path call), and leaves the state the next call orders against.
 ncclResult_t cliqueOrderBefore(Clique* c, int r, hipStream_t s) {
   MpState* mp = c->comms[r] ? c->comms[r]->lt : nullptr;
-  if (mp == nullptr || !mp->streamOrder) return ncclSuccess;
-  hipStreamCaptureStatus cap = hipStreamCaptureStatusNone;
-  HIPCHECK(hipStreamIsCapturing(s, &cap));
-  if (cap != hipStreamCaptureStatusNone) return ncclSuccess;
-  if (mp->lastSeq != 0 && mp->lastStream != s)
-    NCCLCHECK(nbx::launchMpWaitDone((const uint64_t*)mp->orderMem, mp->lastSeq, mp->hostWordsDev, mp->hostWordsDev + 1,
-                                    (uint64_t)(mp->timeoutSec * 1.0e8), s));
-  if (mp->extStream != nullptr && mp->extStream != s)
-    for (hipEvent_t e : mp->extDone) HIPCHECK(hipStreamWaitEvent(s, e, 0));
-  return ncclSuccess;
+  return mp == nullptr ? ncclSuccess : mpWaitPrevious(mp, s);
 }
 
 ncclResult_t cliqueOrderAfter(Clique* c, int r, hipStream_t s) {

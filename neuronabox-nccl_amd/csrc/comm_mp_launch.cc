@@ -47,16 +47,14 @@ ncclResult_t mpLaunchLL(ncclComm* comm, const MpCall& c, MpProto proto, const Mp
   la.recv = c.recv;
   la.count = c.count;
   la.nPacks = (slotBytes + 7) / 8;
-  la.peerLL = mp->peerLLDev;
-  la.myLL = mp->ll;
+  la.peerLL = mp->peers<uint64_t>(kConnLL);
+  la.myLL = mp->own<uint64_t>(kConnLL);
   la.slotLines = mp->llSlotLines;
   la.doneOff = mp->llDoneOff;
   la.planOff = mp->llPlanOff;
   la.state = mp->llState;
   la.blockElts = per > 0 ? per : 1;
-  la.abortWord = mp->hostWordsDev;
-  la.errWord = mp->hostWordsDev + 1;
-  la.timeoutTicks = (uint64_t)(mp->timeoutSec * 1.0e8);
+  mpWaitArgs(mp, &la);
   la.rank = me;
   la.nRanks = n;
   la.postOp = 1;
@@ -89,10 +87,10 @@ ncclResult_t mpLaunchLL(ncclComm* comm, const MpCall& c, MpProto proto, const Mp
     la.nSegs = nSegs;
   }
   if (proto == kMpLL128 || proto == kMpLL128x2) {
-    la.peerL128 = mp->peerL128Dev;
-    la.myL128 = mp->l128;
+    la.peerL128 = mp->peers<uint64_t>(kConnL128);
+    la.myL128 = mp->own<uint64_t>(kConnL128);
     la.l128SlotLines = mp->l128SlotLines;
-    la.l128Bytes = (uint32_t)mp->l128Bytes;
+    la.l128Bytes = (uint32_t)mp->conn[kConnL128].bytes;
     if (proto == kMpLL128x2) {
       la.nSegs = 0;   // never grouped (runMpGroup)
       la.nLines = mp->l128SlotLines / 2;   // sub-slot lines: [parity][RS|AG][source]
@@ -171,13 +169,11 @@ ncclResult_t mpLaunchSimple(ncclComm* comm, const MpCall* calls, int nc, bool tr
   } else {
     sa.nRounds = (blockBytes + grid * slice - 1) / (grid * slice);
   }
-  sa.peerStage = mp->peerStageDev;
-  sa.peerFlags = mp->peerSFlagsDev;
+  sa.peerStage = mp->peers<char>(kConnStage);
+  sa.peerFlags = mp->peers<uint64_t>(kConnFlags);
   sa.counters = mp->scounters;
   sa.stageSlice = mp->sliceBytes;
-  sa.abortWord = mp->hostWordsDev;
-  sa.errWord = mp->hostWordsDev + 1;
-  sa.timeoutTicks = (uint64_t)(mp->timeoutSec * 1.0e8);
+  mpWaitArgs(mp, &sa);
   sa.rank = me;
   sa.nRanks = n;
   sa.mode = transport                  ? nbx::kSimpleTransport
@@ -197,6 +193,20 @@ ncclResult_t mpLaunchSimple(ncclComm* comm, const MpCall* calls, int nc, bool tr
   // launch record (nbx_debug.h): unroll 0, the kernel picks it from its source count
   nbx::logCollLaunch(ring ? nbx::kFamSimpleRing : nbx::kFamSimple, n, 0,
                      (sa.checkSlices ? nbx::kLaunchChecked : 0) | ((int)sa.nSegs << nbx::kLaunchSegsShift));
+  return ncclSuccess;
+}
+
+ncclResult_t mpWaitPrevious(MpState* mp, hipStream_t stream, bool* ordered) {
+  hipStreamCaptureStatus cap = hipStreamCaptureStatusNone;
+  HIPCHECK(hipStreamIsCapturing(stream, &cap));
+  const bool order = cap == hipStreamCaptureStatusNone && mp->streamOrder;
+  if (ordered) *ordered = order;
+  if (!order) return ncclSuccess;
+  if (mp->lastSeq != 0 && mp->lastStream != stream)
+    NCCLCHECK(nbx::launchMpWaitDone((const uint64_t*)mp->orderMem, mp->lastSeq, mpWaitWords(mp).abort,
+                                    mpWaitWords(mp).err, mpTimeoutTicks(mp), stream));
+  if (mp->extStream != nullptr && mp->extStream != stream)   // clique: after a fold-path call
+    for (hipEvent_t e : mp->extDone) HIPCHECK(hipStreamWaitEvent(stream, e, 0));
   return ncclSuccess;
 }
 
@@ -402,6 +412,6 @@ NBX_EXPORT ncclResult_t nbxDebugLinkProbe(ncclComm_t comm, size_t bytesPerPeer, 
   DevGuard g(comm->device);
   if (mp->probeSink == nullptr) HIPCHECK(hipMalloc((void**)&mp->probeSink, nbx::kLinkProbeSinkWords * sizeof(uint32_t)));
   *bytesMovedPerPeer = (size_t)(passes * perPass);
-  return nbx::launchLinkProbe(mp->peerStageDev, comm->rank, n, part, chunkPacks, wg, (int)passes, pull != 0,
+  return nbx::launchLinkProbe(mp->peers<char>(kConnStage), comm->rank, n, part, chunkPacks, wg, (int)passes, pull != 0,
                               mp->probeSink, (hipStream_t)stream);
 }

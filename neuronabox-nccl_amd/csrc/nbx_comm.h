@@ -3,8 +3,11 @@
 // visibility, -fvisibility=hidden):
 //   nccl_api.cc        argument checks, hostToDevRedOp, the one-rank path,
 //                      enqueue, the collective / group / redop / error entry points
+//   comm_mp_settings.cc  NCCL_PROTO / NCCL_ALGO, the reference knobs, every setting and
+//                      buffer layout of a transport (mpSettings; no HIP calls)
+//   comm_mp_connect.cc connection buffers: pool, allocation, IPC mapping check, peer tables
 //   comm_mp_init.cc    multi-process communicator (ncclCommInitRank, nranks > 1):
-//                      settings, connection buffers, IPC mapping check, LL128 probe
+//                      creation, the settings every rank must share, LL128 probe
 //   comm_mp_launch.cc  multi-process launches: protocol choice, LL / LL128 /
 //                      Simple kernels, cross-stream order, group batching
 //   comm_clique.cc     in-process clique (ncclCommInitAll): event-ordered fold,
@@ -19,6 +22,7 @@
 #include <cstdint>
 #include <cstring>
 #include <deque>
+#include <functional>
 #include <memory>
 #include <mutex>
 #include <thread>
@@ -93,7 +97,7 @@ struct ncclComm {
   int blocking = 1;
   // ncclConfig_t minCTAs / maxCTAs after NCCL_MIN_CTAS / NCCL_MAX_CTAS
   // (init.cc:1455-1494); NCCL_CONFIG_UNDEF_INT: not set. A CTA (channel) is a
-  // workgroup here: they bound the transports' grids (mpTransportSettings).
+  // workgroup here: they bound the transports' grids (mpSettings).
   int minCTAs = NCCL_CONFIG_UNDEF_INT;
   int maxCTAs = NCCL_CONFIG_UNDEF_INT;
   int cgaClusterSize = NCCL_CONFIG_UNDEF_INT;   // accepted and kept (no clusters on CDNA)
@@ -219,8 +223,22 @@ ncclResult_t parseConfig(const ncclConfig_t* config, ncclConfig_t* out);
 // ---- comm_clique.cc
 ncclResult_t flushPending();   // launch every complete collective queued for every clique
 
-// ---- multi-process transport state (comm_mp_init.cc)
+// ---- multi-process transport state (comm_mp_settings.cc, comm_mp_connect.cc, comm_mp_init.cc)
 constexpr int kMaxMpRanks = nbx::kSimpleMaxRanks;   // one staging source region per rank
+
+// The connection buffers of a rank, uncached and mapped by every peer:
+//   LL     (nbx_ll.h) [2][n][llSlotLines] lines + [n] done words + plan words
+//   L128   (nbx_ll.h kLL128Coll) [2][n][l128SlotLines] 64-B lines; shares the LL
+//          buffer's done words and parity credits; absent when n > 8
+//   Stage  (nbx_simple.h) staging [2][slots][n][grid][slice], then the plan headers
+//   Flags  (nbx_simple.h) flag words [4][n][grid]
+enum { kConnLL, kConnL128, kConnStage, kConnFlags, kNumConn };
+struct ConnBuf {
+  void* own = nullptr;           // this rank's buffer (nullptr: the communicator has none)
+  uint64_t bytes = 0;            // used bytes; the mapping check's region follows (connAllocBytes)
+  hipIpcMemHandle_t handle{};    // taken at allocation (one process per rank)
+  void** peersDev = nullptr;     // device table of every rank's buffer (own entry: own)
+};
 
 struct MpState {
   nbx::Bootstrap* bs = nullptr;
@@ -228,36 +246,26 @@ struct MpState {
   int* hostWordsDev = nullptr;
   double timeoutSec = 300.0;
   std::vector<void*> peerMaps;         // every IPC mapping this communicator opened (closed at destroy)
-  // LL protocol (nbx_ll.h): own buffer [2][n][slotLines] lines + [n] done words
-  uint64_t* ll = nullptr;
-  uint64_t** peerLLDev = nullptr;
+  ConnBuf conn[kNumConn];
+  template <class T = void> T* own(int t) const { return (T*)conn[t].own; }
+  template <class T> T** peers(int t) const { return (T**)conn[t].peersDev; }
+  // LL protocol (nbx_ll.h)
   uint64_t llMaxBytes = 0;
   uint64_t llSlotLines = 0;
   uint64_t llDoneOff = 0;
   uint64_t llPlanOff = 0;   // plan words [parity 2][source n] (nbx_ll.h)
   nbx::LLState* llState = nullptr;  // device-resident LL-family sequencing (nbx_ll_args.h)
-  // LL128 protocol (nbx_ll.h kLL128Coll): own buffer [2][n][l128SlotLines] 64-B lines;
-  // shares the LL buffer's done words and parity credits
-  uint64_t* l128 = nullptr;
-  uint64_t** peerL128Dev = nullptr;
+  // LL128 protocol (nbx_ll.h kLL128Coll)
   uint64_t l128MaxBytes = 0;        // 0: LL128 unavailable (n > 8)
   uint64_t l128OneShotMax = 0;      // AllReduce, n > 2: one-shot up to this, two-shot above
   uint64_t l128SlotLines = 0;
-  uint64_t l128Bytes = 0;
   int protoMask = 0;                // NCCL_PROTO at init: kProtoLL | kProtoLL128 | kProtoSimple
   bool ring = false;                // NCCL_ALGO=Ring at init
   bool multiGpu = false;            // the ranks span more than one physical GPU (PCI key)
-  // Simple protocol (nbx_simple.h): staging [2][slots][n][grid][slice] and flag
-  // words [4][n][grid] (uncached, IPC-mapped by every peer), counters [4][n][grid]
-  char* stage = nullptr;
-  uint64_t stageBytes = 0;
-  uint64_t llBytes = 0, sflagsBytes = 0;   // used bytes of the LL buffer and the Simple flag words
+  // Simple protocol (nbx_simple.h): staging and flag words above, counters [4][n][grid]
   uint64_t stageHdrOff = 0;         // the Simple plan headers' offset in the staging (after the slices)
   int ipcRepairs = 0;               // connection buffers re-exported at init because a mapping was wrong (mpConnect)
-  uint64_t* sflags = nullptr;
   uint64_t* scounters = nullptr;
-  char** peerStageDev = nullptr;
-  uint64_t** peerSFlagsDev = nullptr;
   uint32_t* probeSink = nullptr;    // nbxDebugLinkProbe's never-written pull sink (allocated on first use)
   uint64_t sliceBytes = 0;          // NBX_SIMPLE_SLICE_BYTES: staging bytes per (slot, source, workgroup)
   int slots = 2;                    // NBX_SIMPLE_SLOTS
@@ -271,7 +279,6 @@ struct MpState {
   // completion word of the communicator's kernels (MpDone, nbx_ll_args.h):
   // [0, 8) done (last completed eager call), [64, 64 + 9 * 64) arrival counters
   char* orderMem = nullptr;
-  hipIpcMemHandle_t llHandle{}, l128Handle{}, stageHandle{}, sflagsHandle{};   // taken at allocation
   uint64_t callSeq = 0;             // eager calls numbered from 1
   uint64_t lastSeq = 0;             // number of the previous eager call that launched a kernel
   uint64_t curSeq = 0;              // number of the call being launched (0: captured)
@@ -297,20 +304,54 @@ inline MpState* mpOf(const ncclComm* c) { return c->mp ? c->mp : c->lt; }
 enum { kProtoLL = 1, kProtoLL128 = 2, kProtoSimple = 4, kProtoAll = 7 };
 enum MpProto : int { kMpLL = 0, kMpLL128 = 1, kMpSimple = 2, kMpLL128x2 = 3 };
 
+// ---- comm_mp_settings.cc
 int protoFromString(const char* v);
 int protoGateAcrossGpus(int mask, bool multiGpu, const char* ncclProto);
 MpProto chooseProtoFor(int mask, bool twoShotKind, uint64_t slotBytes, uint64_t blockBytes, int n, uint64_t llMax,
                        uint64_t l128Max, uint64_t oneShotMax);
-bool algoRingFromEnv();
 long envLong(const char* name, long dflt);
-ncclResult_t mpAllocLL(MpState* mp, int n, bool ipc, const ncclComm* comm);
-void mpTransportSettings(MpState* mp, int minCus, int maxShare, const ncclComm* comm);
-ncclResult_t mpAllocSimple(MpState* mp, int n, bool ipc);
+void mpSettings(MpState* mp, int n, int minCus, int maxShare, bool multiGpu, int minCTAs, int maxCTAs,
+                bool checkPointers);
+// nbxDebugCommSettings' slots, then nbxDebugTransportSettings' further ones (nbx_debug.h)
+constexpr int kNumCommSettings = 11, kNumSettingsValues = 16;
+void mpSettingsValues(const MpState* mp, int64_t v[kNumSettingsValues]);
+
+// ---- comm_mp_connect.cc
+// What the ranks of a multi-process communicator exchange once their buffers
+// are allocated (among ranks running the same build: the layout is free).
+constexpr int kNumAgreed = 11;   // the settings every rank must share (comm_mp_init.cc kAgreed)
+struct MpInitInfo {
+  int32_t device;
+  hipIpcMemHandle_t handle[kNumConn];
+  uint64_t nonce;                // this communicator's mapping self-check pattern (mpConnect)
+  uint64_t agreed[kNumAgreed];
+};
+// The transport's device state and its connection buffers (exported when
+// `ipc`; Simple staging, flag words and counters when `simple`), zeroed.
+ncclResult_t mpAlloc(MpState* mp, int n, bool ipc, bool simple, const ncclComm* comm);
+ncclResult_t mpConnect(ncclComm* c, const std::vector<MpInitInfo>& all);
+// The device tables of every rank's buffers, for the buffers this rank has:
+// peerOf(j, t) is rank j's buffer t as this rank's kernels reach it.
+ncclResult_t connUploadTables(MpState* mp, int n, const std::function<void*(int, int)>& peerOf);
+void mpFreeState(MpState* mp, int device);
+void mpFree(ncclComm* c);
+
+// ---- comm_mp_init.cc
 ncclResult_t mpInit(ncclComm* c, const ncclUniqueId& id);
 ncclResult_t mpLL128SelfTest(ncclComm* c);
 void mpReportDeviceError(ncclComm* c);
-void mpFreeState(MpState* mp, int device);
-void mpFree(ncclComm* c);
+
+// What every device wait of a transport polls, and for how long: the pinned
+// host abort / error words (ncclComm::hostWords) and NBX_TIMEOUT_SEC in 10 ns ticks.
+struct MpWaitWords { int *abort, *err; };
+inline MpWaitWords mpWaitWords(const MpState* mp) { return {mp->hostWordsDev, mp->hostWordsDev + 1}; }
+inline uint64_t mpTimeoutTicks(const MpState* mp) { return (uint64_t)(mp->timeoutSec * 1.0e8); }
+template <class Args>
+void mpWaitArgs(const MpState* mp, Args* a) {   // LLArgs / SimpleArgs
+  a->abortWord = mpWaitWords(mp).abort;
+  a->errWord = mpWaitWords(mp).err;
+  a->timeoutTicks = mpTimeoutTicks(mp);
+}
 
 // ---- comm_mp_launch.cc
 MpProto mpProtoOf(const ncclComm* comm, const MpCall& c);
@@ -324,6 +365,11 @@ ncclResult_t localPreOp(ncclComm* comm, int device, PendingColl* c, int nRanks);
 ncclResult_t preScratchDone(ncclComm* comm, int device, hipStream_t stream);
 ncclResult_t runMpGroup(ncclComm* comm);
 ncclResult_t flushMpGroups();
+// *ordered (when asked for): calls on `stream` are numbered now (no capture,
+// stream order on); then `stream` first waits for the transport's previous call
+// if that ran on another stream (its completion word; after a clique's
+// fold-path call, every rank's extDone event)
+ncclResult_t mpWaitPrevious(MpState* mp, hipStream_t stream, bool* ordered = nullptr);
 
 // One call of a multi-process communicator, ordered after the previous one:
 // the kernels share the communicator's device-resident sequencing, and NCCL's
@@ -344,14 +390,8 @@ ncclResult_t flushMpGroups();
 template <class Launch>
 ncclResult_t runMpOrdered(ncclComm* comm, hipStream_t stream, Launch&& launch) {
   MpState* mp = mpOf(comm);
-  hipStreamCaptureStatus cap = hipStreamCaptureStatusNone;
-  HIPCHECK(hipStreamIsCapturing(stream, &cap));
-  const bool order = cap == hipStreamCaptureStatusNone && mp->streamOrder;
-  if (order && mp->lastSeq != 0 && mp->lastStream != stream)
-    NCCLCHECK(nbx::launchMpWaitDone((const uint64_t*)mp->orderMem, mp->lastSeq, mp->hostWordsDev, mp->hostWordsDev + 1,
-                                    (uint64_t)(mp->timeoutSec * 1.0e8), stream));
-  if (order && mp->extStream != nullptr && mp->extStream != stream)   // clique: after a fold-path call
-    for (hipEvent_t e : mp->extDone) HIPCHECK(hipStreamWaitEvent(stream, e, 0));
+  bool order = false;
+  NCCLCHECK(mpWaitPrevious(mp, stream, &order));
   mp->curSeq = order ? mp->callSeq + 1 : 0;
   mp->launched = false;
   NCCLCHECK(launch());

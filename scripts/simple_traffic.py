@@ -45,7 +45,7 @@ def main():
     ys = [torch.full((count,), -1.0, device="cuda") for _ in range(n)]
     send = (ctypes.c_void_p * n)(*[x.data_ptr() for x in xs])
     recv = (ctypes.c_void_p * n)(*[y.data_ptr() for y in ys])
-    grid = min(128, 256 // n)   # the communicator's grid for n ranks sharing one GPU (mpTransportSettings)
+    grid = min(128, 256 // n)   # the communicator's grid for n ranks sharing one GPU (mpSettings)
     ms = ctypes.c_float()
     rc = lib.nbxDebugSimpleRun(n, 0, ring, count, 7, 0, send, recv, 0, grid, 64 << 10, 2, 1, iters, ctypes.byref(ms))
     exp = torch.zeros(count, device="cuda")

@@ -32,7 +32,7 @@ pytestmark = pytest.mark.gpu
 # created and released after it was destroyed, as an application's are: from
 # the second communicator on they are device memory allocated after
 # communicators came and went in the process, next to the connection buffers
-# the library keeps for the next communicator (comm_mp_init.cc allocSyncMem;
+# the library keeps for the next communicator (comm_mp_connect.cc allocSyncMem;
 # DESIGN §6.4). Every rank compares its send buffers with what it uploaded at
 # the end, so a report can tell a wrong output from a changed input.
 GUARD = 16          # bytes of 0xA5 either side of every output

@@ -434,7 +434,7 @@ def l128_slot_lines(max_bytes: int) -> int:
 
 def proto_of(kind: str, count: int, eb: int, n: int, settings: dict, proto_mask: int = 7,
              oneshot_max: int = 256 << 10) -> str:
-    """The protocol a call takes (comm_mp_init.cc chooseProtoFor), for the
+    """The protocol a call takes (comm_mp_settings.cc chooseProtoFor), for the
     description: "LL", "LL128", "LL128x2" or "Simple"."""
     slot = count * eb
     lo, hi = block_range(count, eb, n, 0)

@@ -23,7 +23,7 @@ from tests.conftest import gpu_order_key
 from tests.edges import cases as edges
 
 K, M = 1 << 10, 1 << 20
-LL_MAX, LL128_MAX, ONESHOT_MAX = 64 * K, 1 * M, 256 * K   # the defaults (comm_mp_init.cc mpAllocLL)
+LL_MAX, LL128_MAX, ONESHOT_MAX = 64 * K, 1 * M, 256 * K   # the defaults (comm_mp_settings.cc mpSettings)
 
 
 @pytest.fixture(scope="module")

@@ -29,7 +29,7 @@ from tests.matrix import inputs as mi
 
 F32, F64 = mi.F32, mi.F64
 K, M = 1 << 10, 1 << 20
-LL_MAX, LL128_MAX, ONESHOT_MAX = 64 * K, 1 * M, 256 * K   # the defaults (comm_mp_init.cc mpAllocLL)
+LL_MAX, LL128_MAX, ONESHOT_MAX = 64 * K, 1 * M, 256 * K   # the defaults (comm_mp_settings.cc mpSettings)
 ITER_BYTES = {16: 65536, 8: 32768, 4: 16384}              # one simpleFoldU iteration: U x 256 packs x 16 B
 
 

@@ -184,7 +184,7 @@ def test_diagnose_collective_names_the_missing_source_and_cell(capsys):
     assert f" = without_rank3={changed}," in last and last.endswith(f" cells 1 top b6r0w9:{changed}")
     assert len(last) < 250
     assert capsys.readouterr().err.startswith(summary)
-    # protocol choice as comm_mp_init.cc chooseProtoFor at these settings
+    # protocol choice as comm_mp_settings.cc chooseProtoFor at these settings
     assert mp_diag.proto_of("ar", 1000, 4, 8, settings) == "LL"
     assert mp_diag.proto_of("ar", 50003, 4, 8, settings) == "LL128"
     assert mp_diag.proto_of("ar", 262144, 4, 8, settings) == "LL128x2"
@@ -193,7 +193,7 @@ def test_diagnose_collective_names_the_missing_source_and_cell(capsys):
 
 
 def test_proto_of_matches_the_library():
-    """mp_diag.proto_of restates comm_mp_init.cc chooseProtoFor: checked
+    """mp_diag.proto_of restates comm_mp_settings.cc chooseProtoFor: checked
     against the library's own (nbxDebugChooseProto) over sizes, kinds, ranks."""
     import ctypes
     from tests.conftest import load_package

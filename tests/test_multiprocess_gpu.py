@@ -1785,7 +1785,8 @@ def _child_knobs(uid_bytes, rank, n, q, env, cfg=None):
     NCCL_LL128_BUFFSIZE, NCCL_MAX/MIN_NCHANNELS) as the communicator applies
     them, then exact AllReduces at an LL, an LL128 and a Simple size. `env`:
     per-rank environment set before ncclCommInitRank (values may differ by
-    rank: {name: [value of rank 0, value of rank 1, ...]})."""
+    rank: {name: [value of rank 0, value of rank 1, ...]}, None: unset). A
+    failed creation returns its code and the error's detail text."""
     try:
         import ctypes
         import os
@@ -1793,7 +1794,10 @@ def _child_knobs(uid_bytes, rank, n, q, env, cfg=None):
         import torch
         from tests.conftest import load_package
         for k, vals in env.items():
-            os.environ[k] = vals[rank]
+            if vals[rank] is None:
+                os.environ.pop(k, None)
+            else:
+                os.environ[k] = vals[rank]
         nbx = load_package()
         lib = nbx.load_library()
         torch.cuda.set_device(0)
@@ -1804,7 +1808,7 @@ def _child_knobs(uid_bytes, rank, n, q, env, cfg=None):
             else:   # ncclConfig_t fields (minCTAs / maxCTAs ...)
                 comm, rc = nbx.Communicator.init_rank_config(n, uid, rank, **cfg)
         except nbx.NcclError as e:
-            q.put((rank, "ok", {"init": int(e.code)}))
+            q.put((rank, "ok", {"init": int(e.code), "detail": str(e)}))
             return
         vals = (ctypes.c_int64 * 10)()
         got = lib.nbxDebugCommSettings(comm.handle, vals, 10)
@@ -1898,19 +1902,35 @@ def test_multiprocess_nbx_override_wins(nbx, monkeypatch):
         assert all(res[r][c] for c in (2048, 131072, 1 << 20)), res[r]
 
 
+# the message group (comm_mp_init.cc kAgreed / kAgreedDiffer) a differing knob is reported under
+_LAYOUT_GROUP = "NCCL_ALGO / NBX_SIMPLE_MAX_GRID / NBX_SIMPLE_SLICE_BYTES / NBX_SIMPLE_SLOTS differ"
+_PROTO_GROUP = "NCCL_PROTO / NBX_LL_MAX_BYTES / NBX_LL128_MAX_BYTES / NBX_LL128_ONESHOT_MAX differ"
+AGREE_GROUP = {"NCCL_BUFFSIZE": _LAYOUT_GROUP, "NCCL_ALGO": _LAYOUT_GROUP, "NCCL_LL_BUFFSIZE": _PROTO_GROUP,
+               "NCCL_PROTO": _PROTO_GROUP, "NBX_GROUP_BATCH": "NBX_GROUP_BATCH differs",
+               "NBX_CHECK_PLANS": "NBX_CHECK_PLANS / NCCL_CHECK_POINTERS differ",
+               "NBX_CHECK_SLICES": "NBX_CHECK_SLICES differs"}
+
+
 @pytest.mark.parametrize("name,vals", [("NCCL_BUFFSIZE", ["65536", "32768"]), ("NBX_GROUP_BATCH", ["1", "0"]),
-                                       ("NCCL_LL_BUFFSIZE", ["65536", "32768"]), ("NBX_CHECK_PLANS", ["1", "0"])])
+                                       ("NCCL_LL_BUFFSIZE", ["65536", "32768"]), ("NBX_CHECK_PLANS", ["1", "0"]),
+                                       ("NCCL_ALGO", ["Ring", None]), ("NBX_CHECK_SLICES", ["1", "0"]),
+                                       ("NCCL_PROTO", ["LL", "Simple"])])
 def test_multiprocess_settings_must_agree(nbx, monkeypatch, name, vals):
     """Settings that decide a call's protocol, grid, staging layout or launch
     cut must be equal on every rank: ncclCommInitRank fails with
-    ncclInvalidUsage on every rank instead of the ranks' kernels disagreeing."""
+    ncclInvalidUsage on every rank instead of the ranks' kernels disagreeing,
+    and the error's detail names the message group of the knob that differs
+    (one knob per group of comm_mp_init.cc kAgreed, and a second one of the two
+    groups that hold several)."""
     monkeypatch.setenv("NBX_BOOTSTRAP_TIMEOUT", "60")
     monkeypatch.setenv("NBX_TIMEOUT_SEC", "60")
-    for k in ("NBX_SIMPLE_SLICE_BYTES", "NBX_LL_MAX_BYTES", "NBX_GROUP_BATCH", "NBX_CHECK_PLANS"):
+    for k in ("NBX_SIMPLE_SLICE_BYTES", "NBX_LL_MAX_BYTES", "NBX_GROUP_BATCH", "NBX_CHECK_PLANS", "NCCL_ALGO",
+              "NBX_CHECK_SLICES", "NCCL_PROTO"):
         monkeypatch.delenv(k, raising=False)
     res = _run_ranks(nbx, 2, _child_knobs, {name: vals})
     for r in range(2):
         assert res[r]["init"] == int(nbx.ncclResult.ncclInvalidUsage), (r, res[r])
+        assert AGREE_GROUP[name] + " across ranks" in res[r]["detail"], (r, res[r])
 
 
 @pytest.mark.parametrize("buf", [0, 1, 2, 3])
