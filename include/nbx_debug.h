@@ -66,7 +66,9 @@ int nbxDebugCommProtoMask(ncclComm_t comm);
  * batching, [8] connection buffers re-exported at creation because a peer's
  * IPC mapping of them showed other memory (verified before first use), [9]
  * plan checks on (NBX_CHECK_PLANS / NCCL_CHECK_POINTERS), [10] Simple slice
- * checksums on (NBX_CHECK_SLICES). Writes min(nOut, 11) values and returns that
+ * checksums on (NBX_CHECK_SLICES), [11] built-in ncclSum / ncclAvg accumulate
+ * in fp32 on fp16, bf16 and fp8 (NBX_WIDE_ACCUM; include/nbx_reduce.h
+ * nbxRedOpCreateWide). Writes min(nOut, 12) values and returns that
  * count; -1 for a bad handle or a communicator without a multi-rank transport. */
 int nbxDebugCommSettings(ncclComm_t comm, int64_t* out, int nOut);
 
@@ -78,7 +80,8 @@ int nbxDebugCommSettings(ncclComm_t comm, int64_t* out, int nOut);
  * communicator's NCCL_CHECK_POINTERS. out[0..10] as nbxDebugCommSettings
  * ([8], re-exports, is 0), [11] protocol mask (as nbxDebugGatedProtoMask),
  * [12] ring schedule (NCCL_ALGO=Ring), [13] LL128 one-shot max bytes, [14] LL
- * lines per slot, [15] LL128 lines per slot. Writes min(nOut, 16) values and
+ * lines per slot, [15] LL128 lines per slot, [16] NBX_WIDE_ACCUM
+ * (nbxDebugCommSettings' [11]). Writes min(nOut, 17) values and
  * returns that count; -1 for a NULL out, nRanks outside 2..64, minCus or
  * maxShare below 1. */
 int nbxDebugTransportSettings(int nRanks, int minCus, int maxShare, int multiGpu, int minCTAs, int maxCTAs,
@@ -232,8 +235,12 @@ int nbxDebugReleaseStream(int hold);
  * fold (16 for <= 2, 8 for <= 4, else 4: nbx_simple.h simpleFold), which the
  * host does not know. flags: bit 0 the checking instantiation (LL family:
  * plan checks, NBX_CHECK_PLANS / NCCL_CHECK_POINTERS; Simple: slice
- * checksums, NBX_CHECK_SLICES), bits 8.. the segments of a group's calls run
- * as one launch (0: a single call). A call is recorded on the thread that
+ * checksums, NBX_CHECK_SLICES), bit 1 the fp32-accumulating instantiation
+ * (a handle of nbxRedOpCreateWide, or NBX_WIDE_ACCUM; its Simple fold unrolls
+ * 8 / 4 / 4 at <= 2 / <= 4 / more sources; never family 12: a wide call on a
+ * ring communicator is family 11), bits 8.. the segments of a group's calls
+ * run as one launch (0: a single call). An in-process clique's fold of a wide
+ * call leaves the wide core's records (families 6 / 7 / 16). A call is recorded on the thread that
  * launches it, after the launch succeeded: the caller's thread for
  * ncclAllReduce / ncclReduceScatter / ncclReduce outside a group, the thread
  * of the outermost ncclGroupEnd for grouped calls. The LL128 self-test of

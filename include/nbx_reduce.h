@@ -120,6 +120,39 @@ ncclResult_t nbxReduceMultiWide(void* const* dsts, int nDsts,
                                 ncclDataType_t dstType, nbxDevRedOpFull op,
                                 int nPreOpSrcs, ncclStream_t stream);
 
+/* The same sum inside the collectives: an operator for ncclAllReduce /
+ * ncclReduceScatter / ncclReduce on `comm`:
+ * base = ncclSum or ncclAvg over `datatype` (fp16, bf16, fp8 e4m3 / e5m2),
+ * accumulated in fp32 and narrowed once. Destroyed with ncclRedOpDestroy.
+ * Every rank's input is widened once, the inputs are added in fp32 in the
+ * direct schedule's operand order (block b of an AllReduce or ReduceScatter:
+ * ranks b+1, ..., b; a Reduce: root+1, ..., root) and the result is narrowed
+ * once: nbxReduceMultiWide's arithmetic over those sources, bit for bit, where
+ * the per-step operators round to `datatype` after every rank (the reference's
+ * rule). ncclAvg multiplies EVERY input by the fp32 scalar of
+ * nbxHostToDevRedOp(&op, ncclAvg, ncclFloat32, nRanks) before the adds. The
+ * bytes between the ranks are today's: every direct schedule (LL, LL128 one-
+ * and two-shot, direct Simple, the in-process clique's fold) moves raw inputs,
+ * and only the fold differs. The protocol is chosen as for any call. The ring
+ * schedule moves partials of `datatype`, so on a communicator created with
+ * NCCL_ALGO=Ring a Simple-sized wide call runs the direct schedule — every
+ * rank decides that from the operator all ranks pass alike. At one rank the
+ * result is the input. The handle lives in the communicator's user-operator
+ * table like a PreMulSum handle: ncclRedOpDestroy frees it, a call with
+ * another datatype is ncclInvalidArgument, its state is copied at enqueue, and
+ * calls with it can be captured in a graph as per-step calls can.
+ * ncclInvalidArgument for a NULL op or comm, a base other than ncclSum /
+ * ncclAvg (a user handle included), a datatype outside the four.
+ * NBX_WIDE_ACCUM=1 at communicator creation (equal on every rank) gives the
+ * built-in ncclSum / ncclAvg on the four types this operator on that
+ * communicator, for programs that cannot call a new function; unset or 0,
+ * nothing changes.
+ * Not provided: a wide PreMulSum with per-rank scalars (each rank's scalar
+ * would have to travel with its input), an fp32 output, Prod / Min / Max
+ * (Min / Max are exact already), a wide ring schedule. */
+ncclResult_t nbxRedOpCreateWide(ncclRedOp_t* op, ncclRedOp_t base,
+                                ncclDataType_t datatype, ncclComm_t comm);
+
 /* One bucket of a batched reduction (same meaning as nbxReduceMulti's arguments). */
 typedef struct {
   void* const* dsts;

@@ -169,6 +169,7 @@ _SIGS = {
                            ctypes.c_void_p],
     "nbxReduceMultiWideBatch": [ctypes.POINTER(ReduceTask), ctypes.c_int, ctypes.c_int, ctypes.c_int, DevRedOpFull,
                                 ctypes.c_int, ctypes.c_void_p],
+    "nbxRedOpCreateWide": [ctypes.POINTER(ctypes.c_int), ctypes.c_int, ctypes.c_int, ctypes.c_void_p],
     "nbxSetLaunchConfig": [ctypes.c_int, ctypes.c_int],
     "nbxGetLaunchConfig": [ctypes.POINTER(ctypes.c_int), ctypes.POINTER(ctypes.c_int)],
     "nbxKernelCount": [],
@@ -598,6 +599,14 @@ class Communicator:
         op = ctypes.c_int()
         _check(load_library().ncclRedOpCreatePreMulSum(ctypes.byref(op), ctypes.c_void_p(scalar_ptr), int(dtype),
                                                        int(residence), self.handle), "ncclRedOpCreatePreMulSum")
+        return op.value
+
+    def redop_create_wide(self, base: int, dtype: int) -> int:
+        """nbxRedOpCreateWide: ncclSum / ncclAvg over fp16, bf16 or fp8, accumulated in fp32 and narrowed
+        once, for this communicator's all_reduce / reduce_scatter / reduce; freed by redop_destroy."""
+        op = ctypes.c_int()
+        _check(load_library().nbxRedOpCreateWide(ctypes.byref(op), int(base), int(dtype), self.handle),
+               "nbxRedOpCreateWide")
         return op.value
 
     def redop_destroy(self, op: int) -> None:

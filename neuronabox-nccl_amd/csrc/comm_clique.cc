@@ -23,7 +23,7 @@ bool sameCollective(const std::vector<PendingColl>& parts) {
   const PendingColl& p0 = parts[0];
   for (size_t r = 1; r < parts.size(); r++)
     if (parts[r].kind != p0.kind || parts[r].count != p0.count || parts[r].dt != p0.dt ||
-        parts[r].root != p0.root || parts[r].op.op != p0.op.op)
+        parts[r].root != p0.root || parts[r].op.op != p0.op.op || parts[r].wide != p0.wide)
       return false;
   return true;
 }
@@ -79,7 +79,7 @@ ncclResult_t foldBlocksBatched(const std::vector<const PendingColl*>& colls, con
     for (; j < blocks.size(); j++) {
       const PendingColl& pj = *colls[j];
       if (pj.dt != pi.dt || pj.op.op != pi.op.op || pj.op.scalarArg != pi.op.scalarArg ||
-          pj.op.scalarArgIsPtr != pi.op.scalarArgIsPtr)
+          pj.op.scalarArgIsPtr != pi.op.scalarArgIsPtr || pj.wide != pi.wide)
         break;
       const RankBlock& b = blocks[j];
       if (b.len == 0) continue;
@@ -132,9 +132,14 @@ ncclResult_t runCliqueColl(Clique* c, const std::vector<PendingColl>& parts0) {
     RankBlock cb = cliqueBlock(parts, n, r);
     if (cb.len == 0) continue;
     NBX_TRACE("clique reduce rank %d len=%zu dst=%p src0=%p", r, cb.len, cb.dsts[0], cb.srcs[0]);
-    NCCLCHECK(nbx::reduceMultiEx(cb.dsts.data(), (int)cb.dsts.size(), cb.srcs.data(), n, cb.len, p0.dt, parts[r].op,
-                                 /*nPreOpSrcs=*/n, /*postOp=*/1, (ncclStream_t)parts[r].stream,
-                                 nbx::kReduceAcquireSystem));
+    if (p0.wide)   // the fp32-accumulating core: the same left fold in fp32, one narrowing (ordered passes past 8 ranks)
+      NCCLCHECK(nbx::reduceMultiWideEx(cb.dsts.data(), (int)cb.dsts.size(), cb.srcs.data(), n, cb.len, p0.dt, p0.dt,
+                                       parts[r].op, /*nPreOpSrcs=*/n, (ncclStream_t)parts[r].stream,
+                                       nbx::kReduceAcquireSystem));
+    else
+      NCCLCHECK(nbx::reduceMultiEx(cb.dsts.data(), (int)cb.dsts.size(), cb.srcs.data(), n, cb.len, p0.dt, parts[r].op,
+                                   /*nPreOpSrcs=*/n, /*postOp=*/1, (ncclStream_t)parts[r].stream,
+                                   nbx::kReduceAcquireSystem));
   }
   // evReduced only orders the pull gather (n > 8); each marker costs ~5 us of
   // device time per stream (scripts/probe_order_cost.hip)
@@ -243,13 +248,15 @@ ncclResult_t runCliqueBatch(Clique* c, const std::vector<std::vector<PendingColl
 // Run a group's queued collectives in order: maximal runs of batchable ones
 // (same collective on every rank, same per-rank streams, no gather step, no
 // buffer dependency on an earlier member of the run, at most kMaxCliqueBatch)
-// as one batch, the rest one by one.
+// as one batch, the rest one by one. A wide call (fp32-accumulating) is not
+// batchable: the batched fold is the per-step core's.
 constexpr size_t kMaxCliqueBatch = 64;
 
 ncclResult_t runCliqueRounds(Clique* c, const std::vector<std::vector<PendingColl>>& rounds) {
   const int n = c->n;
   auto batchable = [&](const std::vector<PendingColl>& parts) {
-    return sameCollective(parts) && !(parts[0].kind == kAllReduce && n > NBX_MAX_DSTS) && !parts[0].localPre;
+    return sameCollective(parts) && !(parts[0].kind == kAllReduce && n > NBX_MAX_DSTS) && !parts[0].localPre &&
+           !parts[0].wide;
   };
   size_t i = 0;
   while (i < rounds.size()) {

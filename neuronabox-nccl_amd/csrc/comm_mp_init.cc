@@ -48,13 +48,15 @@ const Agreed kAgreed[kNumAgreed] = {
     // a checking rank would wait for plan words a non-checking peer never stamps
     NBX_AGREED(3, checkPlans),
     // a checking consumer would compare against sums a non-checking producer never stamps
-    NBX_AGREED(4, checkSlices)};
+    NBX_AGREED(4, checkSlices),
+    // a wide rank and a per-step rank would fold the same lines differently
+    NBX_AGREED(5, wideAccum)};
 #undef NBX_AGREED
 const char* const kAgreedDiffer[] = {
     "NCCL_PROTO / NBX_LL_MAX_BYTES / NBX_LL128_MAX_BYTES / NBX_LL128_ONESHOT_MAX differ across ranks",
     "NCCL_ALGO / NBX_SIMPLE_MAX_GRID / NBX_SIMPLE_SLICE_BYTES / NBX_SIMPLE_SLOTS differ across ranks",
     "NBX_GROUP_BATCH differs across ranks", "NBX_CHECK_PLANS / NCCL_CHECK_POINTERS differ across ranks",
-    "NBX_CHECK_SLICES differs across ranks"};
+    "NBX_CHECK_SLICES differs across ranks", "NBX_WIDE_ACCUM differs across ranks"};
 
 }  // namespace
 
@@ -339,8 +341,9 @@ NBX_EXPORT int nbxDebugCommProtoMask(ncclComm_t comm) {
 // [2] Simple slice bytes, [3] Simple slots, [4] Simple grid, [5] LL grid cap,
 // [6] LL128 grid cap, [7] group batching, [8] connection buffers re-exported
 // at creation because a peer's mapping of them was wrong (mpConnect), [9] plan
-// checks on (NBX_CHECK_PLANS / NCCL_CHECK_POINTERS). Returns
-// how many were written, -1
+// checks on (NBX_CHECK_PLANS / NCCL_CHECK_POINTERS), [10] slice checksums on
+// (NBX_CHECK_SLICES), [11] built-in Sum / Avg accumulate in fp32 on the 16-bit
+// and fp8 types (NBX_WIDE_ACCUM). Returns how many were written, -1
 // for a bad handle or a communicator without that transport.
 NBX_EXPORT int nbxDebugCommSettings(ncclComm_t comm, int64_t* out, int nOut) {
   if (comm == nullptr || comm->magic != kCommMagic || out == nullptr) return -1;
@@ -351,6 +354,7 @@ NBX_EXPORT int nbxDebugCommSettings(ncclComm_t comm, int64_t* out, int nOut) {
   mpSettingsValues(mp, v);
   int k = 0;
   for (; k < nOut && k < kNumCommSettings; k++) out[k] = v[k];
+  if (k == kNumCommSettings && k < nOut) out[k++] = v[kSettingWideAccum];
   return k;
 }
 

@@ -64,11 +64,15 @@ ncclResult_t mpLaunchLL(ncclComm* comm, const MpCall& c, MpProto proto, const Mp
   la.root = c.root;
   la.order = mpOrderArgs(mp);
   la.gridCap = proto == kMpLL ? mp->llGridCap : mp->l128GridCap;
+  // a wide call's plan differs from the per-step call's of the same device op
+  const int32_t planOp = c.op.op | (c.wide ? nbx::kPlanOpWide : 0);
   // launch record (nbx_debug.h): the kernel family, the checking instantiation
-  // (planSig != 0 picks it in nbx_coll_launch.cc), the group's segments
+  // (planSig != 0 picks it in nbx_coll_launch.cc), the fp32-accumulating one,
+  // the group's segments
   auto launched = [&](ncclResult_t r, int family) {
     if (r == ncclSuccess)
       nbx::logCollLaunch(family, n, 1, (la.planSig != 0 ? nbx::kLaunchChecked : 0) |
+                                           (c.wide ? nbx::kLaunchWideAccum : 0) |
                                            ((int)la.nSegs << nbx::kLaunchSegsShift));
     return r;
   };
@@ -96,22 +100,26 @@ ncclResult_t mpLaunchLL(ncclComm* comm, const MpCall& c, MpProto proto, const Mp
       la.nLines = mp->l128SlotLines / 2;   // sub-slot lines: [parity][RS|AG][source]
       const uint64_t blockLines =
           ((uint64_t)per * (uint64_t)eb + nbx::kL128DataBytesHost - 1) / nbx::kL128DataBytesHost;
-      la.planSig = mp->checkPlans ? nbx::llPlanSig(la, (int32_t)proto, (int32_t)c.dt, c.op.op) : 0;
-      return launched(nbx::launchLL128AllReduce2(c.dt, c.op, la, blockLines, c.stream), nbx::kFamLL128x2);
+      la.planSig = mp->checkPlans ? nbx::llPlanSig(la, (int32_t)proto, (int32_t)c.dt, planOp) : 0;
+      return launched(nbx::launchLL128AllReduce2(c.dt, c.op, la, blockLines, c.stream, c.wide), nbx::kFamLL128x2);
     }
     la.nLines = nSegs > 1 ? units : (slotBytes + nbx::kL128DataBytesHost - 1) / nbx::kL128DataBytesHost;
-    la.planSig = mp->checkPlans ? nbx::llPlanSig(la, (int32_t)proto, (int32_t)c.dt, c.op.op) : 0;
-    return launched(nbx::launchLL128Coll(c.dt, c.op, la, c.stream), nbx::kFamLL128);
+    la.planSig = mp->checkPlans ? nbx::llPlanSig(la, (int32_t)proto, (int32_t)c.dt, planOp) : 0;
+    return launched(nbx::launchLL128Coll(c.dt, c.op, la, c.stream, c.wide), nbx::kFamLL128);
   }
   if (nSegs > 1) la.nPacks = units;
-  la.planSig = mp->checkPlans ? nbx::llPlanSig(la, (int32_t)proto, (int32_t)c.dt, c.op.op) : 0;
-  return launched(nbx::launchLLColl(c.dt, c.op, la, c.stream), nbx::kFamLL);
+  la.planSig = mp->checkPlans ? nbx::llPlanSig(la, (int32_t)proto, (int32_t)c.dt, planOp) : 0;
+  return launched(nbx::launchLLColl(c.dt, c.op, la, c.stream, c.wide), nbx::kFamLL);
 }
 
 // Simple protocol: one kernel (nbx_simple.h). Blocks: AllReduce / Reduce the
 // direct schedule's 16-B aligned blocks (blockRange; the ring's chunks are the
 // same blocks), ReduceScatter the API's recvcount blocks, ring Reduce the
-// whole message as one block (a chain). A call of B-byte blocks runs on
+// whole message as one block (a chain). A wide call (fp32-accumulating, every
+// call of a launch alike: sameOp) runs the direct schedule and its shapes on a
+// ring communicator too — the ring moves partials of the element type, the
+// direct schedule raw inputs — which every rank derives from the operator all
+// ranks pass alike. A call of B-byte blocks runs on
 // min(grid, B / 4 KiB) workgroups in rounds of one slice per workgroup and
 // block, the slice at most the staging slice — every rank derives the same
 // numbers from the same arguments. Several calls of one group (nc > 1, same
@@ -122,11 +130,12 @@ ncclResult_t mpLaunchSimple(ncclComm* comm, const MpCall* calls, int nc, bool tr
   const MpCall& c = calls[0];
   const int n = comm->nRanks, me = comm->rank;
   const uint64_t eb = (uint64_t)typeSize(c.dt);
+  const bool ring = mp->ring && !transport && !c.wide;
   auto shape = [&](const MpCall& m, uint64_t* blockElts, uint64_t* total) {
     if (m.kind == kReduceScatter) {
       *blockElts = m.count;
       *total = (uint64_t)m.count * (uint64_t)n;
-    } else if (m.kind == kReduce && mp->ring) {
+    } else if (m.kind == kReduce && mp->ring && !m.wide) {
       *blockElts = m.count;
       *total = m.count;
     } else {
@@ -185,14 +194,14 @@ ncclResult_t mpLaunchSimple(ncclComm* comm, const MpCall* calls, int nc, bool tr
   sa.gridMax = mp->simpleGrid;
   sa.prefetch = mp->simplePrefetch;
   sa.hdrOff = mp->stageHdrOff;
-  sa.planSig = mp->checkPlans ? nbx::simplePlanSig(sa, (uint32_t)grid, (int32_t)c.dt, c.op.op) : 0;
+  sa.planSig = mp->checkPlans ? nbx::simplePlanSig(sa, (uint32_t)grid, (int32_t)c.dt, c.op.op | (c.wide ? nbx::kPlanOpWide : 0)) : 0;
   sa.checkSlices = mp->checkSlices ? (mp->sliceFaultRank == me ? 2 : 1) : 0;   // 2: test hook, a wrong stamp
   sa.order = mpOrderArgs(mp);
-  const bool ring = mp->ring && !transport;
-  NCCLCHECK(nbx::launchSimple(c.dt, c.op, sa, (unsigned)grid, ring, c.stream));
+  NCCLCHECK(nbx::launchSimple(c.dt, c.op, sa, (unsigned)grid, ring, c.stream, c.wide));
   // launch record (nbx_debug.h): unroll 0, the kernel picks it from its source count
   nbx::logCollLaunch(ring ? nbx::kFamSimpleRing : nbx::kFamSimple, n, 0,
-                     (sa.checkSlices ? nbx::kLaunchChecked : 0) | ((int)sa.nSegs << nbx::kLaunchSegsShift));
+                     (sa.checkSlices ? nbx::kLaunchChecked : 0) | (c.wide ? nbx::kLaunchWideAccum : 0) |
+                         ((int)sa.nSegs << nbx::kLaunchSegsShift));
   return ncclSuccess;
 }
 
@@ -306,7 +315,7 @@ ncclResult_t runMpGroup(ncclComm* comm) {
   };
   auto sameOp = [](const MpCall& a, const MpCall& b) {
     return a.kind == b.kind && a.dt == b.dt && a.op.op == b.op.op && a.op.scalarArg == b.op.scalarArg &&
-           a.op.scalarArgIsPtr == b.op.scalarArgIsPtr && (a.kind != kReduce || a.root == b.root);
+           a.op.scalarArgIsPtr == b.op.scalarArgIsPtr && a.wide == b.wide && (a.kind != kReduce || a.root == b.root);
   };
   try {
     size_t i = 0;

@@ -97,6 +97,12 @@ long envLong(const char* name, long dflt) {
   return (v && *v) ? std::atol(v) : dflt;
 }
 
+// NBX_WIDE_ACCUM=1: an unmodified NCCL program cannot call nbxRedOpCreateWide,
+// so with it the built-in ncclSum / ncclAvg on f16, bf16 and fp8 take the
+// fp32-accumulating operator on every communicator created under it (the
+// ranks of one must agree: their kernels differ). Unset or 0: nothing changes.
+bool wideAccumFromEnv() { return envLong("NBX_WIDE_ACCUM", 0) != 0; }
+
 // The reference's own tuning knobs on this path, read at communicator
 // creation like NCCL reads them (init.cc:523-541 computeBuffSizes,
 // connect.cc:314-315, tuning.cc:12), each mapped onto the setting that plays
@@ -203,6 +209,7 @@ void mpSettings(MpState* mp, int n, int minCus, int maxShare, bool multiGpu, int
   // consumer hash every element (off by default; equal on every rank).
   mp->checkSlices = envLong("NBX_CHECK_SLICES", 0) != 0;
   mp->sliceFaultRank = (int)envLong("NBX_DEBUG_SLICE_FAULT", -1);
+  mp->wideAccum = wideAccumFromEnv();
   // LL buffer: 2 parities x n sources x 2 lines per 8-byte pack
   {
     uint64_t mx = (uint64_t)ncclEnvMapped("NBX_LL_MAX_BYTES", "NCCL_LL_BUFFSIZE", 64 << 10, 1, 2);
@@ -236,7 +243,7 @@ void mpSettingsValues(const MpState* mp, int64_t v[kNumSettingsValues]) {
       (int64_t)mp->llMaxBytes, (int64_t)mp->l128MaxBytes, (int64_t)mp->sliceBytes, mp->slots, mp->simpleGrid,
       (int64_t)mp->llGridCap, (int64_t)mp->l128GridCap, mp->groupBatch, mp->ipcRepairs, mp->checkPlans,
       mp->checkSlices, mp->protoMask, mp->ring, (int64_t)mp->l128OneShotMax, (int64_t)mp->llSlotLines,
-      (int64_t)mp->l128SlotLines};
+      (int64_t)mp->l128SlotLines, mp->wideAccum};
   std::copy(s, s + kNumSettingsValues, v);
 }
 

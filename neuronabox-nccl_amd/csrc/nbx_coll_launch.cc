@@ -3,6 +3,7 @@
 // is device-resident; the communicator layer (comm_mp_launch.cc) builds the
 // arguments and records the launch.
 #include <cstdlib>
+#include <mutex>
 
 #include "nbx_launch.h"
 #include "nbx_ll_args.h"
@@ -39,50 +40,94 @@ const KernelSet* collKernels(ncclDataType_t dt, const nbxDevRedOpFull& op) {
   return &table()[(int)dt][op.op];
 }
 
+// The fp32-accumulating kernels (nbx_wide_coll.h): their own table, so
+// KernelSet and nbxKernelCount stay as they are.
+WideCollTable g_wideColl;
+std::once_flag g_wideCollOnce;
+const WideCollSet* wideCollKernels(ncclDataType_t dt, const nbxDevRedOpFull& op) {
+  std::call_once(g_wideCollOnce, [] {
+    std::memset(&g_wideColl, 0, sizeof(g_wideColl));
+    fillWideColl16(g_wideColl);
+    fillWideColl8(g_wideColl);
+  });
+  if ((int)dt < 0 || (int)dt >= kNumTypes || !g_wideColl[(int)dt].valid) return nullptr;
+  if ((op.op != nbxDevSum && op.op != nbxDevPreMulSum) || op.scalarArgIsPtr) return nullptr;
+  return &g_wideColl[(int)dt];
+}
+
+// The one instantiation's scalar (FnWide): the PreMulSum's fp32 bits, 1.0f for a Sum.
+template <class A>
+void setWideScalarArg(A& a, const nbxDevRedOpFull& op) {
+  a.arg = op.op == nbxDevPreMulSum ? (op.scalarArg & 0xffffffffull) : 0x3f800000ull;
+  a.argPtr = nullptr;
+}
+
 // One LL-family launch: the plain kernel, or the one with plan words when
 // a.planSig != 0; `units` packs or lines at unitsPerBlock per 256-thread
 // workgroup, capped by the environment and by a.gridCap.
 ncclResult_t launchLLFamily(ncclDataType_t dt, const nbxDevRedOpFull& op, LLArgs& a, const void* KernelSet::*plain,
-                            const void* KernelSet::*checked, uint64_t units, size_t unitsPerBlock, size_t (*maxGrid)(),
-                            hipStream_t stream) {
-  const KernelSet* ks = collKernels(dt, op);
-  if (ks == nullptr || !ks->valid || ks->*plain == nullptr || ks->*checked == nullptr) return ncclInvalidArgument;
-  setScalarArg(a, op);
+                            const void* KernelSet::*checked, const void* WideCollSet::*widePlain,
+                            const void* WideCollSet::*wideChecked, bool wide, uint64_t units, size_t unitsPerBlock,
+                            size_t (*maxGrid)(), hipStream_t stream) {
+  const void* kPlain = nullptr;
+  const void* kChecked = nullptr;
+  if (wide) {
+    const WideCollSet* ws = wideCollKernels(dt, op);
+    if (ws == nullptr) return ncclInvalidArgument;
+    kPlain = ws->*widePlain;
+    kChecked = ws->*wideChecked;
+    setWideScalarArg(a, op);
+  } else {
+    const KernelSet* ks = collKernels(dt, op);
+    if (ks == nullptr || !ks->valid) return ncclInvalidArgument;
+    kPlain = ks->*plain;
+    kChecked = ks->*checked;
+    setScalarArg(a, op);
+  }
+  if (kPlain == nullptr || kChecked == nullptr) return ncclInvalidArgument;
   size_t grid = (units + unitsPerBlock - 1) / unitsPerBlock;
   if (grid < 1) grid = 1;
   if (grid > maxGrid()) grid = maxGrid();
   if (a.gridCap != 0 && grid > a.gridCap) grid = a.gridCap;
   void* args[] = {&a};
-  hipError_t e = hipLaunchKernel(a.planSig != 0 ? ks->*checked : ks->*plain, dim3((unsigned)grid), dim3(256), args, 0,
-                                 stream);
+  hipError_t e = hipLaunchKernel(a.planSig != 0 ? kChecked : kPlain, dim3((unsigned)grid), dim3(256), args, 0, stream);
   return e != hipSuccess ? ncclUnhandledCudaError : ncclSuccess;
 }
 }  // namespace
 
-ncclResult_t launchLLColl(ncclDataType_t dt, const nbxDevRedOpFull& op, LLArgs& a, hipStream_t stream) {
-  return launchLLFamily(dt, op, a, &KernelSet::ll, &KernelSet::llChk, a.nPacks, 256, llMaxGrid, stream);
+ncclResult_t launchLLColl(ncclDataType_t dt, const nbxDevRedOpFull& op, LLArgs& a, hipStream_t stream, bool wide) {
+  return launchLLFamily(dt, op, a, &KernelSet::ll, &KernelSet::llChk, &WideCollSet::ll, &WideCollSet::llChk, wide,
+                        a.nPacks, 256, llMaxGrid, stream);
 }
 
-ncclResult_t launchLL128Coll(ncclDataType_t dt, const nbxDevRedOpFull& op, LLArgs& a, hipStream_t stream) {
-  return launchLLFamily(dt, op, a, &KernelSet::ll128, &KernelSet::ll128Chk, a.nLines, kLL128LinesPerBlock,
-                        ll128MaxGrid, stream);
+ncclResult_t launchLL128Coll(ncclDataType_t dt, const nbxDevRedOpFull& op, LLArgs& a, hipStream_t stream, bool wide) {
+  return launchLLFamily(dt, op, a, &KernelSet::ll128, &KernelSet::ll128Chk, &WideCollSet::ll128,
+                        &WideCollSet::ll128Chk, wide, a.nLines, kLL128LinesPerBlock, ll128MaxGrid, stream);
 }
 
 ncclResult_t launchLL128AllReduce2(ncclDataType_t dt, const nbxDevRedOpFull& op, LLArgs& a, uint64_t blockLines,
-                                   hipStream_t stream) {
-  return launchLLFamily(dt, op, a, &KernelSet::ll128x2, &KernelSet::ll128x2Chk, blockLines, kLL128LinesPerBlock,
-                        ll128MaxGrid, stream);
+                                   hipStream_t stream, bool wide) {
+  return launchLLFamily(dt, op, a, &KernelSet::ll128x2, &KernelSet::ll128x2Chk, &WideCollSet::ll128x2,
+                        &WideCollSet::ll128x2Chk, wide, blockLines, kLL128LinesPerBlock, ll128MaxGrid, stream);
 }
 
 ncclResult_t launchSimple(ncclDataType_t dt, const nbxDevRedOpFull& op, SimpleArgs& a, unsigned grid, bool ring,
-                          hipStream_t stream) {
-  const KernelSet* ks = collKernels(dt, op);
-  if (ks == nullptr) return ncclInvalidArgument;
-  const void* k = a.checkSlices ? (ring ? ks->simpleRingChk : ks->simpleChk) : (ring ? ks->simpleRing : ks->simple);
-  if (!ks->valid || k == nullptr || grid < 1 || grid > (unsigned)a.gridMax || a.gridMax > kSimpleMaxGrid ||
+                          hipStream_t stream, bool wide) {
+  const void* k = nullptr;
+  if (wide) {
+    const WideCollSet* ws = ring ? nullptr : wideCollKernels(dt, op);   // the ring moves partials: no wide form
+    if (ws == nullptr) return ncclInvalidArgument;
+    k = a.checkSlices ? ws->simpleChk : ws->simple;
+  } else {
+    const KernelSet* ks = collKernels(dt, op);
+    if (ks == nullptr || !ks->valid) return ncclInvalidArgument;
+    k = a.checkSlices ? (ring ? ks->simpleRingChk : ks->simpleChk) : (ring ? ks->simpleRing : ks->simple);
+  }
+  if (k == nullptr || grid < 1 || grid > (unsigned)a.gridMax || a.gridMax > kSimpleMaxGrid ||
       a.nRanks < 2 || a.nRanks > kSimpleMaxRanks)
     return ncclInvalidArgument;
-  setScalarArg(a, op);
+  if (wide) setWideScalarArg(a, op);
+  else setScalarArg(a, op);
   void* args[] = {&a};
   hipError_t e = hipLaunchKernel(k, dim3(grid), dim3(kBlock), args, 0, stream);
   return e != hipSuccess ? ncclUnhandledCudaError : ncclSuccess;

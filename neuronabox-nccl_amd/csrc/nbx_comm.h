@@ -82,6 +82,7 @@ struct UserRedOp {   // comm.h ncclUserRedOp
   int freeNext;      // -1 = allocated
   ncclDataType_t datatype;
   nbxDevRedOpFull opFull;
+  bool wide;         // nbxRedOpCreateWide: Sum, or PreMulSum with the fp32 scalar 1 / nRanks, accumulated in fp32
 };
 
 struct Clique;
@@ -103,6 +104,7 @@ struct ncclComm {
   int cgaClusterSize = NCCL_CONFIG_UNDEF_INT;   // accepted and kept (no clusters on CDNA)
   int splitShare = NCCL_CONFIG_UNDEF_INT;       // accepted and kept (children share nothing here)
   bool checkPointers = false;
+  bool wideAccum = false;   // NBX_WIDE_ACCUM at creation: ncclSum / ncclAvg on f16, bf16, fp8 take the wide operator
   std::atomic<int> asyncError{ncclSuccess};
   std::mutex opsMu;
   std::vector<nbxcomm::UserRedOp> userOps;
@@ -155,6 +157,11 @@ struct PendingColl {
   // peers' own scalars for the direct paths (:617-628), so the result is
   // sum_r s_r * x_r. Run as a pre-pass into scratch, then a Sum (localPreOp).
   bool localPre = false;
+  // an fp32-accumulating sum (nbxRedOpCreateWide, NBX_WIDE_ACCUM): op is Sum, or
+  // the PreMulSum of wide Avg (fp32 scalar by value, applied to EVERY rank's
+  // input in the fold: never localPre). The multi-rank kernels take the wide
+  // instantiation, the clique's fold the wide core.
+  bool wide = false;
 };
 
 // One reducing collective as enqueued on a multi-process communicator (the
@@ -210,7 +217,15 @@ bool spansConflict(const std::vector<Span>& a, const std::vector<Span>& b);
 ncclResult_t commCheck(ncclComm* comm, const char* opName);
 ncclResult_t commEnsureReady(ncclComm* comm);
 ncclRedOp_t userRedOpMangle(ncclComm* comm, ncclRedOp_t op);
-ncclResult_t hostToDevRedOp(nbxDevRedOpFull* opFull, ncclRedOp_t op, ncclDataType_t dt, ncclComm* comm);
+// *wide (when asked for): the operator accumulates in fp32 (a handle of
+// nbxRedOpCreateWide, or ncclSum / ncclAvg on a 16-bit or fp8 type under
+// NBX_WIDE_ACCUM=1); opFull is then Sum, or PreMulSum with fp32 scalar bits.
+ncclResult_t hostToDevRedOp(nbxDevRedOpFull* opFull, ncclRedOp_t op, ncclDataType_t dt, ncclComm* comm,
+                            bool* wide = nullptr);
+// The types the fp32-accumulating sums exist for, and their operator state:
+// base ncclSum -> Sum; ncclAvg -> PreMulSum by 1 / nRanks in fp32.
+bool wideType(ncclDataType_t dt);
+ncclResult_t wideRedOp(nbxDevRedOpFull* opFull, ncclRedOp_t base, int nRanks);
 // Element range of block b when `count` is split over n ranks, aligned so
 // every block starts on a 16-byte boundary relative to the buffer.
 void blockRange(size_t count, int eb, int n, int b, size_t* off, size_t* len);
@@ -287,6 +302,7 @@ struct MpState {
   bool groupBatch = true;           // NBX_GROUP_BATCH=0: every grouped call its own kernel
   bool checkPlans = false;          // NBX_CHECK_PLANS (default NCCL_CHECK_POINTERS): plan words / headers
   bool checkSlices = false;         // NBX_CHECK_SLICES: Simple slices carry a checksum the consumer verifies
+  bool wideAccum = false;           // NBX_WIDE_ACCUM (as ncclComm::wideAccum; here to be reported and checked equal)
   int sliceFaultRank = -1;          // NBX_DEBUG_SLICE_FAULT (test hook): this rank's workgroup 0 stamps wrong sums
   std::vector<hipEvent_t> groupEvents;   // fan-in / fan-out of a group launch over several streams
   // clique ranks only: the previous call ran on the event-ordered fold path
@@ -313,13 +329,15 @@ long envLong(const char* name, long dflt);
 void mpSettings(MpState* mp, int n, int minCus, int maxShare, bool multiGpu, int minCTAs, int maxCTAs,
                 bool checkPointers);
 // nbxDebugCommSettings' slots, then nbxDebugTransportSettings' further ones (nbx_debug.h)
-constexpr int kNumCommSettings = 11, kNumSettingsValues = 16;
+// (nbxDebugCommSettings' slot 11 is the last value here, NBX_WIDE_ACCUM)
+constexpr int kNumCommSettings = 11, kNumSettingsValues = 17, kSettingWideAccum = 16;
+bool wideAccumFromEnv();   // NBX_WIDE_ACCUM, read at communicator creation
 void mpSettingsValues(const MpState* mp, int64_t v[kNumSettingsValues]);
 
 // ---- comm_mp_connect.cc
 // What the ranks of a multi-process communicator exchange once their buffers
 // are allocated (among ranks running the same build: the layout is free).
-constexpr int kNumAgreed = 11;   // the settings every rank must share (comm_mp_init.cc kAgreed)
+constexpr int kNumAgreed = 12;   // the settings every rank must share (comm_mp_init.cc kAgreed)
 struct MpInitInfo {
   int32_t device;
   hipIpcMemHandle_t handle[kNumConn];

@@ -226,6 +226,9 @@ struct FnBase {
   using Elt = E;
   static constexpr bool kHasPre = false;
   static constexpr bool kHasPost = false;
+  // the fp32-accumulating functors of the collectives (nbx_wide_coll.h) set
+  // this: a fold site then keeps a WideAcc instead of an accumulator of Elt
+  static constexpr bool kWide = false;
   // cap on the big-tile unroll: VALU-heavy functors gain nothing from more
   // loads in flight and only grow code size
   static constexpr int kUnrollCap = 16;
@@ -239,6 +242,16 @@ struct FnBase {
   __device__ u32x4 redPack(u32x4 a, u32x4 b) const { return packRed(*static_cast<const D*>(this), a, b); }
   __device__ u32x4 prePack(u32x4 a) const { return packPre(*static_cast<const D*>(this), a); }
   __device__ u32x4 postPack(u32x4 a) const { return packPost(*static_cast<const D*>(this), a); }
+};
+
+// The accumulator a collective's fold site keeps beside its accumulator of
+// codes: nothing for a per-step functor, the fp32 pairs of WORDS dwords of
+// codes for a wide one (Fn::kWP pairs per dword; Fn::foldWord / narrowWord).
+template <class Fn, int WORDS, bool = Fn::kWide>
+struct WideAcc {};
+template <class Fn, int WORDS>
+struct WideAcc<Fn, WORDS, true> {
+  f32x2 f[WORDS * Fn::kWP] = {};
 };
 
 // -------------------------------------------------------------------------

@@ -147,4 +147,21 @@ struct WideSet {
   int valid;
 };
 
+// Launch table for one element type of the collectives' fp32-accumulating
+// folds (nbx_wide_coll.h: the direct-schedule kernels of nbx_ll.h and
+// nbx_simple.h over FnWide). A table of its own, as WideSet: KernelSet and
+// nbxKernelCount stay as they are. There is no ring entry: the ring moves
+// partials of the element type.
+struct WideCollSet {
+  const void* ll;
+  const void* ll128;
+  const void* ll128x2;
+  const void* llChk;        // the same three with plan words (NBX_CHECK_PLANS)
+  const void* ll128Chk;
+  const void* ll128x2Chk;
+  const void* simple;       // Simple protocol, direct schedule
+  const void* simpleChk;    // with slice checksums (NBX_CHECK_SLICES)
+  int valid;
+};
+
 }  // namespace nbx

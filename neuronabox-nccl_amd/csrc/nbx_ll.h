@@ -296,6 +296,7 @@ __global__ __launch_bounds__(256) void kLLColl(LLArgs a) {
     }
     Pk acc;
     acc.u = 0;
+    WideAcc<Fn, 2> wacc;   // a wide functor's fp32 accumulator of the pack (per-step: nothing)
     for (int q = 0; q < n; q++) {
       const int j = (first + q) % n;
       Pk x;
@@ -321,13 +322,19 @@ __global__ __launch_bounds__(256) void kLLColl(LLArgs a) {
         }
         x.u = (l0 & 0xffffffffull) | (l1 << 32);
       }
+      if constexpr (Fn::kWide) {   // widened and scaled once, added in fp32; narrowed behind the loop
+        fn.foldWord(&wacc.f[0], (uint32_t)x.u, q == 0);
+        fn.foldWord(&wacc.f[Fn::kWP], (uint32_t)(x.u >> 32), q == 0);
+      } else {
 #pragma unroll
-      for (int e = 0; e < EPK; e++) {
-        E v = x.e[e];
-        if constexpr (Fn::kHasPre) v = fn.pre(v);   // PreMulSum: every contribution pre-multiplied once
-        acc.e[e] = q == 0 ? v : fn.red(acc.e[e], v);
+        for (int e = 0; e < EPK; e++) {
+          E v = x.e[e];
+          if constexpr (Fn::kHasPre) v = fn.pre(v);   // PreMulSum: every contribution pre-multiplied once
+          acc.e[e] = q == 0 ? v : fn.red(acc.e[e], v);
+        }
       }
     }
+    if constexpr (Fn::kWide) acc.u = fn.narrowWord(&wacc.f[0]) | ((uint64_t)fn.narrowWord(&wacc.f[Fn::kWP]) << 32);
     if constexpr (Fn::kHasPost) {
       if (a.postOp) {
 #pragma unroll
@@ -493,17 +500,24 @@ __device__ __forceinline__ void l128FoldLine(const Fn& fn, const LLArgs& a, cons
     };
     Pk acc;
     acc.u = 0;
+    WideAcc<Fn, 2> wacc;   // a wide functor's fp32 accumulator of the word (per-step: nothing)
     for (int q = 0; q < n; q++) {
       const int j = first + q < n ? first + q : first + q - n;
       Pk x;
       x.u = l128Pick(v, pz, j, k);
+      if constexpr (Fn::kWide) {   // as kLLColl
+        fn.foldWord(&wacc.f[0], (uint32_t)x.u, q == 0);
+        fn.foldWord(&wacc.f[Fn::kWP], (uint32_t)(x.u >> 32), q == 0);
+      } else {
 #pragma unroll
-      for (int e = 0; e < EPK; e++) {
-        E y = x.e[e];
-        if constexpr (Fn::kHasPre) y = fn.pre(y);   // PreMulSum: every contribution pre-multiplied once
-        acc.e[e] = q == 0 ? y : fn.red(acc.e[e], y);
+        for (int e = 0; e < EPK; e++) {
+          E y = x.e[e];
+          if constexpr (Fn::kHasPre) y = fn.pre(y);   // PreMulSum: every contribution pre-multiplied once
+          acc.e[e] = q == 0 ? y : fn.red(acc.e[e], y);
+        }
       }
     }
+    if constexpr (Fn::kWide) acc.u = fn.narrowWord(&wacc.f[0]) | ((uint64_t)fn.narrowWord(&wacc.f[Fn::kWP]) << 32);
     if constexpr (Fn::kHasPost) {
       if (a.postOp) {
 #pragma unroll

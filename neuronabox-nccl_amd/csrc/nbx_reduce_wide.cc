@@ -40,9 +40,10 @@ LazySetting<long long> g_wideShiftMinElts{0, parseWideShiftMinElts};
 // op: as wideScalarOp() returns it.
 ncclResult_t launchWidePass(const WideSet& ws, bool out32, bool partFirst, int layout, size_t head, void* const* dsts,
                             int nDsts, const void* const* srcs, int nSrcs, size_t count, const nbxDevRedOpFull& op,
-                            uint32_t mask, hipStream_t stream) {
+                            uint32_t mask, int acquireSystem, hipStream_t stream) {
   KArgs a;
   fillKArgs(a, dsts, nDsts, srcs, nSrcs, count, op, mask);
+  a.acquireSystem = acquireSystem;
   const int dev = launchDevice(stream);
   const size_t cus = (size_t)cuCount(dev);
   void* args[] = {&a};
@@ -144,13 +145,13 @@ int wideLayout(size_t eb, size_t deb, void* const* dsts, int nDsts, const void* 
   return kWideLayoutShifted;
 }
 
-}  // namespace nbx
-
-using namespace nbx;
-
-NBX_EXPORT ncclResult_t nbxReduceMultiWide(void* const* dsts, int nDsts, const void* const* srcs, int nSrcs,
-                                           size_t count, ncclDataType_t srcType, ncclDataType_t dstType,
-                                           nbxDevRedOpFull op, int nPreOpSrcs, ncclStream_t stream) {
+// nbxReduceMultiWide with the internal flags of reduceMultiEx: with
+// kReduceAcquireSystem every pass's workgroups issue a system-scope acquire
+// before their first load (the clique's fold reads its peers' buffers).
+ncclResult_t reduceMultiWideEx(void* const* dsts, int nDsts, const void* const* srcs, int nSrcs, size_t count,
+                               ncclDataType_t srcType, ncclDataType_t dstType, nbxDevRedOpFull op, int nPreOpSrcs,
+                               ncclStream_t stream, int flags) {
+  const int acq = (flags & kReduceAcquireSystem) ? 1 : 0;
   if (!argArraysOk(dsts, nDsts, srcs, nSrcs)) return ncclInvalidArgument;
   ncclResult_t cr = checkWideOp(srcType, dstType, op);
   if (cr != ncclSuccess) return cr;
@@ -171,7 +172,7 @@ NBX_EXPORT ncclResult_t nbxReduceMultiWide(void* const* dsts, int nDsts, const v
 
   if (nSrcs <= kMaxKSrcs)
     return launchWidePass(ws, out32, false, layout, head, dsts, nDsts, srcs, nSrcs, count, lop,
-                          preMask(pre, nPreOpSrcs, 0, nSrcs, 0), strm);
+                          preMask(pre, nPreOpSrcs, 0, nSrcs, 0), acq, strm);
 
   // > 8 sources (foldPasses) through an fp32 partial that is never narrowed,
   // so the result is the single fp32 left fold. The partial lives in dsts[0]
@@ -190,8 +191,18 @@ NBX_EXPORT ncclResult_t nbxReduceMultiWide(void* const* dsts, int nDsts, const v
                     [&](void* const* d, int nd, const void* const* s, int n, int first, bool partFirst, bool last) {
                       const int slot0 = partFirst ? 1 : 0;
                       return launchWidePass(ws, last ? out32 : true, partFirst, layout, head, d, nd, s, n, count, lop,
-                                            preMask(pre, nPreOpSrcs, first, n - slot0, slot0), strm);
+                                            preMask(pre, nPreOpSrcs, first, n - slot0, slot0), acq, strm);
                     });
+}
+
+}  // namespace nbx
+
+using namespace nbx;
+
+NBX_EXPORT ncclResult_t nbxReduceMultiWide(void* const* dsts, int nDsts, const void* const* srcs, int nSrcs,
+                                           size_t count, ncclDataType_t srcType, ncclDataType_t dstType,
+                                           nbxDevRedOpFull op, int nPreOpSrcs, ncclStream_t stream) {
+  return reduceMultiWideEx(dsts, nDsts, srcs, nSrcs, count, srcType, dstType, op, nPreOpSrcs, stream, 0);
 }
 
 NBX_EXPORT long long nbxDebugSetWideShiftMinElts(long long elts) { return g_wideShiftMinElts.set(elts, elts >= 1); }

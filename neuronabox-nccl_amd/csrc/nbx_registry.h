@@ -28,4 +28,10 @@ void fillWide(WideTable& t);
 // their realigning kernels, per element width (called by fillWide)
 void fillWideShift16(WideTable& t);
 void fillWideShift8(WideTable& t);
+
+// the collectives' fp32-accumulating kernels: one WideCollSet per element
+// type, a unit per element width (inst_wide_coll*.hip)
+typedef WideCollSet WideCollTable[kNumTypes];
+void fillWideColl16(WideCollTable& t);
+void fillWideColl8(WideCollTable& t);
 }  // namespace nbx

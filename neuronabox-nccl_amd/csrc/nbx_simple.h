@@ -350,20 +350,26 @@ __device__ __forceinline__ void simpleCopy(void* d0, bool sys0, void* d1, bool s
 // receive the slice hash of each staging source read (indexed by fold
 // position; nullptr: none read) and of the result stored into the staging
 // destinations (nullptr: none written).
-template <class Fn, int U, bool CHK>
+// A wide functor (Fn::kWide, nbx_wide_coll.h) widens and scales every source
+// once, adds in fp32 (wacc: 8 fp32 per 16-bit pack, 16 per fp8 pack, beside
+// the loaded codes) and narrows once before the stores; preMask and doPost do
+// not apply to it. Its U and G are simpleFold's wide ones, sized to the
+// registers. The slice hashes are over the codes read and the codes stored,
+// so they are the per-step ones.
+template <class Fn, int U, bool CHK, int G = 32 / U>
 __device__ __forceinline__ void simpleFoldU(const Fn& fn, const char* const* srcs, int nSrcs, uint64_t sysSrcMask,
                                             uint64_t preMask, bool doPost, char* const* dsts, int nDsts,
                                             uint64_t sysMask, uint64_t nElts, bool aligned, uint32_t* srcSums,
                                             uint32_t* dstSum) {
   using E = typename Fn::Elt;
   constexpr int EPP = 16 / (int)sizeof(E);
-  constexpr int G = 32 / U;
   uint32_t hd = 0;
   uint64_t done = 0;
   if (aligned) {
     const uint64_t nPk = nElts / EPP;
     for (uint64_t p = threadIdx.x; p < nPk; p += (uint64_t)U * kBlock) {
       u32x4 acc[U];
+      WideAcc<Fn, 4> wacc[U];
       for (int q0 = 0; q0 < nSrcs; q0 += G) {
         u32x4 v[G][U];
 #pragma unroll
@@ -397,8 +403,13 @@ __device__ __forceinline__ void simpleFoldU(const Fn& fn, const char* const* src
 #pragma unroll
             for (int u = 0; u < U; u++) {
               u32x4 t = v[s][u];
-              if constexpr (Fn::kHasPre) if ((preMask >> (q0 + s)) & 1u) t = fn.prePack(t);
-              acc[u] = (q0 + s == 0) ? t : fn.redPack(acc[u], t);
+              if constexpr (Fn::kWide) {
+#pragma unroll
+                for (int w = 0; w < 4; w++) fn.foldWord(&wacc[u].f[w * Fn::kWP], t[w], q0 + s == 0);
+              } else {
+                if constexpr (Fn::kHasPre) if ((preMask >> (q0 + s)) & 1u) t = fn.prePack(t);
+                acc[u] = (q0 + s == 0) ? t : fn.redPack(acc[u], t);
+              }
             }
           }
         }
@@ -406,7 +417,13 @@ __device__ __forceinline__ void simpleFoldU(const Fn& fn, const char* const* src
 #pragma unroll
       for (int u = 0; u < U; u++) {
         if (p + (uint64_t)u * kBlock < nPk) {
-          u32x4 r = acc[u];
+          u32x4 r;
+          if constexpr (Fn::kWide) {
+#pragma unroll
+            for (int w = 0; w < 4; w++) r[w] = fn.narrowWord(&wacc[u].f[w * Fn::kWP]);
+          } else {
+            r = acc[u];
+          }
           if constexpr (Fn::kHasPost) if (doPost) r = fn.postPack(r);
           if constexpr (CHK) if (dstSum) hd += slicePackHash<E>(r, (p + (uint64_t)u * kBlock) * EPP);
           for (int d = 0; d < nDsts; d++) {
@@ -423,12 +440,16 @@ __device__ __forceinline__ void simpleFoldU(const Fn& fn, const char* const* src
     E acc = (sysSrcMask & 1u) ? ldSysElt((const E*)srcs[0] + e) : ldElt((const E*)srcs[0] + e);
     if constexpr (CHK) if (srcSums && (sysSrcMask & 1u)) atomicAdd(&srcSums[0], sliceEltHash(acc, e));
     if constexpr (Fn::kHasPre) if (preMask & 1u) acc = fn.pre(acc);
+    float wa = 0.0f;   // a wide functor's accumulator
+    if constexpr (Fn::kWide) wa = fn.wideElt(acc);
     for (int q = 1; q < nSrcs; q++) {
       E x = ((sysSrcMask >> q) & 1u) ? ldSysElt((const E*)srcs[q] + e) : ldElt((const E*)srcs[q] + e);
       if constexpr (CHK) if (srcSums && ((sysSrcMask >> q) & 1u)) atomicAdd(&srcSums[q], sliceEltHash(x, e));
       if constexpr (Fn::kHasPre) if ((preMask >> q) & 1u) x = fn.pre(x);
-      acc = fn.red(acc, x);
+      if constexpr (Fn::kWide) wa = wa + fn.wideElt(x);
+      else acc = fn.red(acc, x);
     }
+    if constexpr (Fn::kWide) acc = fn.narrowElt(wa);
     if constexpr (Fn::kHasPost) if (doPost) acc = fn.post(acc);
     if constexpr (CHK) if (dstSum) hd += sliceEltHash(acc, e);
     for (int d = 0; d < nDsts; d++) {
@@ -444,7 +465,21 @@ __device__ __forceinline__ void simpleFold(const Fn& fn, const char* const* srcs
                                            uint64_t preMask, bool doPost, char* const* dsts, int nDsts,
                                            uint64_t sysMask, uint64_t nElts, bool aligned,
                                            uint32_t* srcSums = nullptr, uint32_t* dstSum = nullptr) {
-  if (nSrcs <= 2)
+  if constexpr (Fn::kWide) {
+    // 8 / 4 / 4 packs per lane with 2 / 4 / 8 sources' loads in flight: the
+    // fp32 accumulator is 2x (16-bit) or 4x (fp8) the pack registers, so the
+    // per-step 16 / 8 / 4 at 32 packs in flight would not leave a second
+    // workgroup's waves room on a SIMD (DESIGN §7 has the register counts)
+    if (nSrcs <= 2)
+      simpleFoldU<Fn, 8, CHK, 2>(fn, srcs, nSrcs, sysSrcMask, preMask, doPost, dsts, nDsts, sysMask, nElts, aligned,
+                                 srcSums, dstSum);
+    else if (nSrcs <= 4)
+      simpleFoldU<Fn, 4, CHK, 4>(fn, srcs, nSrcs, sysSrcMask, preMask, doPost, dsts, nDsts, sysMask, nElts, aligned,
+                                 srcSums, dstSum);
+    else
+      simpleFoldU<Fn, 4, CHK, 8>(fn, srcs, nSrcs, sysSrcMask, preMask, doPost, dsts, nDsts, sysMask, nElts, aligned,
+                                 srcSums, dstSum);
+  } else if (nSrcs <= 2)
     simpleFoldU<Fn, 16, CHK>(fn, srcs, nSrcs, sysSrcMask, preMask, doPost, dsts, nDsts, sysMask, nElts, aligned, srcSums,
                         dstSum);
   else if (nSrcs <= 4)

@@ -217,6 +217,7 @@ __global__ __launch_bounds__(kBlock) void kWidePacks(KArgs a) {
   using E = typename W::Elt;
   constexpr int EPP = W::kEPP, Q = EPP / 4;
   static_assert(!PART || NSRC >= 2, "a pass that reads a partial folds at least one more source");
+  acquirePeerData(a);   // a clique's fold reads its peers' buffers (reduceMultiWideEx)
   const float sc = loadWideArg(a.argPtr, a.arg);
   const uint64_t head = (uint64_t)a.headElts;
   const u32x4* src[NSRC];
@@ -273,6 +274,7 @@ __global__ __launch_bounds__(kBlock) void kWidePacks(KArgs a) {
 // that is not 16-byte aligned behind the head.
 template <class W, bool OUT32, bool PART>
 __global__ __launch_bounds__(kBlock) void kWideElts(KArgs a) {
+  acquirePeerData(a);
   const float sc = loadWideArg(a.argPtr, a.arg);
   const uint64_t stride = (uint64_t)gridDim.x * kBlock;
   for (uint64_t i = (uint64_t)blockIdx.x * kBlock + threadIdx.x; i < a.nElts; i += stride)
@@ -307,6 +309,7 @@ __global__ __launch_bounds__(kShiftLdsWaves * 64) void kWideShiftedLds(KArgs a) 
   constexpr int P = U * 64 + 1;     // packs per source per stage
   constexpr uint64_t kTile = (uint64_t)U * 64;
   __shared__ u32x4 sm[WV][S][NST][P];
+  acquirePeerData(a);
   const float sc = loadWideArg(a.argPtr, a.arg);
   const uint64_t head = (uint64_t)a.headElts;
   const uint64_t n = a.nPacks;

@@ -119,9 +119,32 @@ ncclRedOp_t userRedOpMangle(ncclComm* comm, ncclRedOp_t op) {
 }
 
 
+bool wideType(ncclDataType_t dt) {
+  return dt == ncclFloat16 || dt == ncclBfloat16 || dt == ncclFloat8e4m3 || dt == ncclFloat8e5m2;
+}
+
+// Wide Avg is the core's PreMulSum with the fp32 scalar of an fp32 ncclAvg
+// (1 / nRanks rounded once), applied to every rank's input, then summed.
+ncclResult_t wideRedOp(nbxDevRedOpFull* opFull, ncclRedOp_t base, int nRanks) {
+  if (base == ncclSum) {
+    *opFull = nbxDevRedOpFull{nbxDevSum, 0, 0};
+    return ncclSuccess;
+  }
+  if (base != ncclAvg) return ncclInvalidArgument;
+  return nbxHostToDevRedOp(opFull, ncclAvg, ncclFloat32, nRanks);
+}
+
 // hostToDevRedOp — enqueue.cc:1436-1512, including the user-op branch.
-ncclResult_t hostToDevRedOp(nbxDevRedOpFull* opFull, ncclRedOp_t op, ncclDataType_t dt, ncclComm* comm) {
-  if ((int)op < (int)ncclNumOps) return nbxHostToDevRedOp(opFull, op, dt, comm->nRanks);
+ncclResult_t hostToDevRedOp(nbxDevRedOpFull* opFull, ncclRedOp_t op, ncclDataType_t dt, ncclComm* comm, bool* wide) {
+  if (wide) *wide = false;
+  if ((int)op < (int)ncclNumOps) {
+    // NBX_WIDE_ACCUM=1: the built-in sums of the narrow types are the wide operator
+    if (wide && comm->wideAccum && (op == ncclSum || op == ncclAvg) && wideType(dt)) {
+      *wide = true;
+      return wideRedOp(opFull, op, comm->nRanks);
+    }
+    return nbxHostToDevRedOp(opFull, op, dt, comm->nRanks);
+  }
   int ix = (int)userRedOpMangle(comm, op) - (int)ncclNumOps;
   std::lock_guard<std::mutex> g(comm->opsMu);
   if (ix < 0 || ix >= (int)comm->userOps.size() || comm->userOps[ix].freeNext != -1) {
@@ -134,6 +157,7 @@ ncclResult_t hostToDevRedOp(nbxDevRedOpFull* opFull, ncclRedOp_t op, ncclDataTyp
     return ncclInvalidArgument;
   }
   *opFull = u.opFull;
+  if (wide) *wide = u.wide;
   return ncclSuccess;
 }
 
@@ -301,18 +325,24 @@ ncclResult_t enqueueColl(CollKind kind, const char* opName, const void* sendbuff
   info("%s: sendbuff %p recvbuff %p count %zu datatype %d op %d root %d comm %p [nranks=%d] stream %p", opName,
        sendbuff, (void*)recvbuff, count, (int)dt, (int)op, root, (void*)comm, comm->nRanks, (void*)stream);
   nbxDevRedOpFull opFull;
-  NCCLCHECK(hostToDevRedOp(&opFull, op, dt, comm));   // op state copied at enqueue (enqueue.cc:1557-1562)
+  bool wide = false;
+  NCCLCHECK(hostToDevRedOp(&opFull, op, dt, comm, &wide));   // op state copied at enqueue (enqueue.cc:1557-1562)
   if (comm->nRanks == 1) {
     DevGuard g(comm->device);
+    // a wide sum or average of one rank is its input: a copy, never the
+    // PreMulSum kernel (a wide Avg carries fp32 scalar bits, not the type's)
+    if (wide) opFull = nbxDevRedOpFull{nbxDevSum, 0, 0};
     ncclResult_t r = launchOneRank(recvbuff, sendbuff, count, opFull, dt, stream);
     if (r != ncclSuccess) comm->asyncError.store(r);
     return r;
   }
   // a user PreMulSum: the scalar is this rank's alone (PendingColl::localPre)
-  const bool localPre = (int)op >= (int)ncclNumOps && opFull.op == nbxDevPreMulSum;
+  // (a wide Avg handle is no user PreMulSum: its scalar multiplies every rank's input, in the fold)
+  const bool localPre = !wide && (int)op >= (int)ncclNumOps && opFull.op == nbxDevPreMulSum;
   if (comm->mp) {
     MpCall call{kind, sendbuff, recvbuff, count, dt, opFull, root, stream};
     call.localPre = localPre;
+    call.wide = wide;
     if (t_groupDepth > 0) {   // run at the outermost ncclGroupEnd
       if (comm->mp->group.empty()) t_groupMpComms.push_back(comm);
       comm->mp->group.push_back(call);
@@ -333,6 +363,7 @@ ncclResult_t enqueueColl(CollKind kind, const char* opName, const void* sendbuff
     std::lock_guard<std::mutex> g(g_pendMu);
     PendingColl pc{kind, sendbuff, recvbuff, count, dt, opFull, root, stream};
     pc.localPre = localPre;
+    pc.wide = wide;
     comm->clique->pending[comm->rank].push_back(pc);
   }
   if (t_groupDepth == 0) return flushPending();
@@ -388,6 +419,7 @@ ncclResult_t newComm(ncclComm** out, int nRanks, int rank, int dev, const ncclCo
   c->device = dev;
   const char* cp = std::getenv("NCCL_CHECK_POINTERS");
   c->checkPointers = cp && std::atoi(cp) != 0;
+  c->wideAccum = wideAccumFromEnv();
   if (nRanks > 1) {
     DevGuard g(dev);
     if (hipHostMalloc((void**)&c->hostWords, 64, hipHostMallocMapped | hipHostMallocCoherent) != hipSuccess ||
@@ -460,6 +492,59 @@ NBX_API(const char*, ncclGetLastError, ncclComm_t comm) {
   return g_lastError;
 }
 
+// A slot of the communicator's user-op table off its free list (enqueue.cc:
+// 1659-1672); the caller holds opsMu and fills the operator in.
+static int userOpAlloc(ncclComm* comm) {
+  if (comm->freeHead == (int)comm->userOps.size()) {
+    int cap = 2 * (int)comm->userOps.size();
+    if (cap < 4) cap = 4;
+    int old = (int)comm->userOps.size();
+    comm->userOps.resize(cap);
+    for (int ix = old; ix < cap; ix++) comm->userOps[ix].freeNext = ix + 1;
+  }
+  const int ix = comm->freeHead;
+  comm->freeHead = comm->userOps[ix].freeNext;
+  comm->userOps[ix].freeNext = -1;
+  return ix;
+}
+
+// nbxRedOpCreateWide (include/nbx_reduce.h): a handle in the same table as the
+// PreMulSum ones — mangled, freed by ncclRedOpDestroy, its datatype checked at
+// the call — whose state is the wide operator's.
+NBX_EXPORT ncclResult_t nbxRedOpCreateWide(ncclRedOp_t* op, ncclRedOp_t base, ncclDataType_t datatype,
+                                           ncclComm_t comm) {
+  // the argument checks come before the communicator is looked at, so they
+  // are the same with or without a device
+  if (comm == nullptr) {
+    warn("nbxRedOpCreateWide : comm argument is NULL");
+    return ncclInvalidArgument;
+  }
+  if (op == nullptr) {
+    warn("nbxRedOpCreateWide : op argument is NULL");
+    return ncclInvalidArgument;
+  }
+  if (base != ncclSum && base != ncclAvg) {
+    warn("nbxRedOpCreateWide : base operation %d is neither ncclSum nor ncclAvg", (int)base);
+    return ncclInvalidArgument;
+  }
+  if (!wideType(datatype)) {
+    warn("nbxRedOpCreateWide : datatype %d is none of fp16, bf16, fp8 e4m3, fp8 e5m2", (int)datatype);
+    return ncclInvalidArgument;
+  }
+  NCCLCHECK(commCheck(comm, "nbxRedOpCreateWide"));
+  NCCLCHECK(commEnsureReady(comm));
+  nbxDevRedOpFull full;
+  NCCLCHECK(wideRedOp(&full, base, comm->nRanks));
+  std::lock_guard<std::mutex> g(comm->opsMu);
+  const int ix = userOpAlloc(comm);
+  UserRedOp& u = comm->userOps[ix];
+  u.datatype = datatype;
+  u.opFull = full;
+  u.wide = true;
+  *op = userRedOpMangle(comm, (ncclRedOp_t)((int)ncclNumOps + ix));
+  return ncclSuccess;
+}
+
 NBX_API(ncclResult_t, ncclRedOpCreatePreMulSum, ncclRedOp_t* op, void* scalar, ncclDataType_t datatype,
         ncclScalarResidence_t residence, ncclComm_t comm) {
   // enqueue.cc:1648-1685
@@ -469,18 +554,10 @@ NBX_API(ncclResult_t, ncclRedOpCreatePreMulSum, ncclRedOp_t* op, void* scalar, n
   const int sz = typeSize(datatype);
   if (sz < 0) return ncclInvalidArgument;
   std::lock_guard<std::mutex> g(comm->opsMu);
-  if (comm->freeHead == (int)comm->userOps.size()) {
-    int cap = 2 * (int)comm->userOps.size();
-    if (cap < 4) cap = 4;
-    int old = (int)comm->userOps.size();
-    comm->userOps.resize(cap);
-    for (int ix = old; ix < cap; ix++) comm->userOps[ix].freeNext = ix + 1;
-  }
-  int ix = comm->freeHead;
+  const int ix = userOpAlloc(comm);
   UserRedOp& u = comm->userOps[ix];
-  comm->freeHead = u.freeNext;
-  u.freeNext = -1;
   u.datatype = datatype;
+  u.wide = false;
   u.opFull.op = nbxDevPreMulSum;
   if (residence == ncclScalarHostImmediate) {
     u.opFull.scalarArgIsPtr = 0;
