@@ -207,6 +207,72 @@ ncclResult_t nbxReduceMultiWideBatch(const nbxReduceTask* tasks, int nTasks,
                                      ncclDataType_t srcType, ncclDataType_t dstType,
                                      nbxDevRedOpFull op, int nPreOpSrcs, ncclStream_t stream);
 
+/* Statistics of a bucket the fp32-accumulating sum has just produced, taken
+ * from the fold's registers: no second pass over the fp32 masters. */
+typedef struct {
+  double   sumSq;     /* sum over i of acc_i * acc_i */
+  float    amax;      /* max over i of |acc_i|, NaN > +inf > every finite value */
+  uint32_t reserved;  /* written as 0 */
+} nbxWideStats;       /* 16 bytes, 8-byte aligned, DEVICE memory */
+
+/* nbxReduceMultiWide that also writes *stats (device memory, overwritten, never
+ * accumulated into). acc_i is element i's final fp32 accumulator BEFORE the
+ * narrowing: the value nbxReduceMultiWide narrows, or stores for an fp32
+ * output. The destinations receive the bits nbxReduceMultiWide gives with the
+ * same arguments: every layout, up to NBX_MAX_SRCS sources, in place.
+ *   amax   exact and order-independent, numpy.max(numpy.abs(acc)): a NaN if
+ *          any acc_i is NaN, else +inf if any is +-inf, else the largest
+ *          |acc_i| (+0.0 for an all-zero bucket). An fp16 output that
+ *          overflows on narrowing still reports the finite magnitude.
+ *   sumSq  NaN if any acc_i is NaN, else +inf if any is inf; else the exact
+ *          sum of acc_i^2 within a relative L * 2^-24, L = 32. L counts the
+ *          fp32 roundings on the longest path into one fp64 partial: a lane
+ *          squares and adds with one fma (one rounding) per element into two
+ *          fp32 sums, one per half of an accumulator pair, for the length of
+ *          one tile, and a tile is at most 4 packs per lane of 16 fp8 elements
+ *          (4+ sources): 4 x 16 / 2 = 32 per sum. 16-bit sources reach 16, the
+ *          realigning kernel 8 / 16, the element kernel and every head or tail
+ *          element 8 or fewer, a batched bucket 4 / 8. Everything above a
+ *          tile is added in fp64 (a few dozen adds on any path: negligible
+ *          against L * 2^-24). The bound holds while the true sum is
+ *          below 2^120 — above that a lane's fp32 sum may overflow and sumSq
+ *          be +inf — and for accumulators whose squares are normal fp32
+ *          numbers (|acc_i| >= 2^-63; smaller squares round to fp32 denormals
+ *          or to zero, an absolute 2^-150 each).
+ * Reproducible: the statistics are a function of the arguments and of the
+ * kernel family and its tile shape alone — not of the grid (nbxSetLaunchConfig
+ * blocksPerCU), the CU count, the static or dynamic tile schedule, or which
+ * workgroup ran which tile. Every tile's waves write one 16-byte partial each
+ * to a slot indexed by tile and wave (stream-ordered scratch, 16 bytes per 64
+ * to 4096 elements), and a second, small kernel sums the slots in a tree fixed
+ * by the slot index. Two identical calls give identical bits.
+ * count == 0 writes {0, 0, 0}. More than 8 sources: only the last pass
+ * contributes (nothing of the intermediate fp32 partial).
+ * Checks as nbxReduceMultiWide, and stats == NULL or not 8-byte aligned:
+ * ncclInvalidArgument; every check before any device call.
+ * Stream-ordered, asynchronous and graph-capturable.
+ * Not provided: statistics inside ncclAllReduce / ncclReduceScatter /
+ * ncclReduce, for the per-step nbxReduceMulti, and a host-staged form. */
+ncclResult_t nbxReduceMultiWideStats(void* const* dsts, int nDsts,
+                                     const void* const* srcs, int nSrcs,
+                                     size_t count, ncclDataType_t srcType,
+                                     ncclDataType_t dstType, nbxDevRedOpFull op,
+                                     int nPreOpSrcs, nbxWideStats* stats,
+                                     ncclStream_t stream);
+
+/* nbxReduceMultiWideBatch that also writes stats[k] for every bucket k
+ * (nTasks entries, overwritten), as if nbxReduceMultiWideStats were called per
+ * bucket: the same destinations, the same definitions and bound; an empty
+ * bucket's record is {0, 0, 0}. A bucket that runs as its own launch (mixed
+ * layout, > 8 sources, no table slot) takes the single call's kernels, so its
+ * sumSq may differ from the batched kernel's in the last bits (another tile
+ * shape); amax never does. Checks as nbxReduceMultiWideBatch; stats == NULL
+ * with nTasks > 0, or not 8-byte aligned: ncclInvalidArgument. */
+ncclResult_t nbxReduceMultiWideBatchStats(const nbxReduceTask* tasks, int nTasks,
+                                          ncclDataType_t srcType, ncclDataType_t dstType,
+                                          nbxDevRedOpFull op, int nPreOpSrcs,
+                                          nbxWideStats* stats, ncclStream_t stream);
+
 /* Host-staged form of nbxReduceMulti: sources and destinations in HOST memory
  * (pinned for full speed; pageable works), the path NCCL's NET/SHM transports
  * stage through (host-pinned proxy FIFOs net.cc:735/883, /dev/shm buffers

@@ -125,6 +125,11 @@ class ReduceTask(ctypes.Structure):
                 ("count", ctypes.c_size_t)]
 
 
+class WideStats(ctypes.Structure):
+    """nbxWideStats (include/nbx_reduce.h): a bucket's statistics, 16 bytes of device memory."""
+    _fields_ = [("sumSq", ctypes.c_double), ("amax", ctypes.c_float), ("reserved", ctypes.c_uint32)]
+
+
 _SIGS = {
     # public ABI (include/nccl.h)
     "ncclGetVersion": [ctypes.POINTER(ctypes.c_int)],
@@ -169,6 +174,11 @@ _SIGS = {
                            ctypes.c_void_p],
     "nbxReduceMultiWideBatch": [ctypes.POINTER(ReduceTask), ctypes.c_int, ctypes.c_int, ctypes.c_int, DevRedOpFull,
                                 ctypes.c_int, ctypes.c_void_p],
+    "nbxReduceMultiWideStats": [ctypes.POINTER(ctypes.c_void_p), ctypes.c_int, ctypes.POINTER(ctypes.c_void_p),
+                                ctypes.c_int, ctypes.c_size_t, ctypes.c_int, ctypes.c_int, DevRedOpFull, ctypes.c_int,
+                                ctypes.c_void_p, ctypes.c_void_p],
+    "nbxReduceMultiWideBatchStats": [ctypes.POINTER(ReduceTask), ctypes.c_int, ctypes.c_int, ctypes.c_int,
+                                     DevRedOpFull, ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p],
     "nbxRedOpCreateWide": [ctypes.POINTER(ctypes.c_int), ctypes.c_int, ctypes.c_int, ctypes.c_void_p],
     "nbxSetLaunchConfig": [ctypes.c_int, ctypes.c_int],
     "nbxGetLaunchConfig": [ctypes.POINTER(ctypes.c_int), ctypes.POINTER(ctypes.c_int)],
@@ -367,6 +377,8 @@ class LaunchFamily(enum.IntEnum):        # include/nbx_debug.h nbxDebugLaunchLog
 
 
 LAUNCH_DYNAMIC, LAUNCH_OUT32, LAUNCH_PART_FIRST = 1, 2, 4
+LAUNCH_STATS = 8   # wide families 6 / 7 / 15 / 16: the STATS form ran (nbxReduceMultiWideStats)
+WIDE_STATS_L = 32  # fp32 roundings into one fp64 partial: sumSq is exact within L * 2^-24 (include/nbx_reduce.h)
 LAUNCH_CHECKED, LAUNCH_SEGS_SHIFT = 1, 8   # collective families: checking instantiation, group segments (batch: buckets)
 LAUNCH_LOG_CAP = 64
 
@@ -433,6 +445,24 @@ def reduce_multi_wide(dsts: Sequence[int], srcs: Sequence[int], count: int, src_
            "nbxReduceMultiWide")
 
 
+def reduce_multi_wide_stats_raw(dsts: Sequence[int], srcs: Sequence[int], count: int, src_type: int, dst_type: int,
+                                op: DevRedOpFull, stats: int, n_pre_op_srcs: int = 0, stream: int = 0) -> int:
+    """Call nbxReduceMultiWideStats (`stats`: device address of an nbxWideStats); returns the code."""
+    d = (ctypes.c_void_p * max(1, len(dsts)))(*[ctypes.c_void_p(int(x)) for x in dsts])
+    s = (ctypes.c_void_p * max(1, len(srcs)))(*[ctypes.c_void_p(int(x)) for x in srcs])
+    return load_library().nbxReduceMultiWideStats(d, len(dsts), s, len(srcs), int(count), int(src_type),
+                                                  int(dst_type), op, int(n_pre_op_srcs), ctypes.c_void_p(int(stats)),
+                                                  ctypes.c_void_p(int(stream)))
+
+
+def reduce_multi_wide_stats(dsts: Sequence[int], srcs: Sequence[int], count: int, src_type: int, dst_type: int,
+                            op: DevRedOpFull, stats: int, n_pre_op_srcs: int = 0, stream: int = 0) -> None:
+    """reduce_multi_wide that also writes the bucket's amax and sum of squares (of the fp32
+    accumulators, before any narrowing) to the 16 device bytes at `stats`."""
+    _check(reduce_multi_wide_stats_raw(dsts, srcs, count, src_type, dst_type, op, stats, n_pre_op_srcs, stream),
+           "nbxReduceMultiWideStats")
+
+
 WIDE_LAYOUT_ELEMENTS, WIDE_LAYOUT_PACKS, WIDE_LAYOUT_REALIGN = 0, 1, 2   # nbxDebugWideLayout
 WIDE_SHIFT_MIN_ELTS_DEFAULT = 2097152   # the measured crossover (include/nbx_debug.h); env NBX_WIDE_SHIFT_MIN_ELTS
 
@@ -481,6 +511,22 @@ def reduce_multi_wide_batch_raw(buckets: Sequence[tuple], src_type: int, dst_typ
     tasks, _keep = _reduce_tasks(buckets)
     return load_library().nbxReduceMultiWideBatch(tasks, len(buckets), int(src_type), int(dst_type), op,
                                                   int(n_pre_op_srcs), ctypes.c_void_p(int(stream)))
+
+
+def reduce_multi_wide_batch_stats_raw(buckets: Sequence[tuple], src_type: int, dst_type: int, op: DevRedOpFull,
+                                      stats: int, n_pre_op_srcs: int = 0, stream: int = 0) -> int:
+    """Call nbxReduceMultiWideBatchStats (`stats`: device address of len(buckets) nbxWideStats)."""
+    tasks, _keep = _reduce_tasks(buckets)
+    return load_library().nbxReduceMultiWideBatchStats(tasks, len(buckets), int(src_type), int(dst_type), op,
+                                                       int(n_pre_op_srcs), ctypes.c_void_p(int(stats)),
+                                                       ctypes.c_void_p(int(stream)))
+
+
+def reduce_multi_wide_batch_stats(buckets: Sequence[tuple], src_type: int, dst_type: int, op: DevRedOpFull,
+                                  stats: int, n_pre_op_srcs: int = 0, stream: int = 0) -> None:
+    """reduce_multi_wide_batch that also writes every bucket's nbxWideStats to stats[k]."""
+    _check(reduce_multi_wide_batch_stats_raw(buckets, src_type, dst_type, op, stats, n_pre_op_srcs, stream),
+           "nbxReduceMultiWideBatchStats")
 
 
 def reduce_multi_wide_batch(buckets: Sequence[tuple], src_type: int, dst_type: int, op: DevRedOpFull,

@@ -147,6 +147,27 @@ struct WideSet {
   int valid;
 };
 
+// Bucket statistics of the fp32-accumulating sums (nbxReduceMultiWideStats,
+// nbx_wide.h "Bucket statistics"). The STATS kernels take the slot array as a
+// second kernel argument, so KArgs and BatchListArgs are what they were.
+struct WideSlot {      // one tile's (and wave's) partial: 16 bytes, one dwordx4 store
+  double sumSq;
+  float amax;          // IEEE max: a NaN element shows in sumSq only
+  uint32_t pad;
+};
+constexpr int kWideEltsStatTile = 8;      // elements per lane per tile of kWideEltsStats
+constexpr int kWideStatsFan = 4096;       // slots one workgroup of kWideStatsReduce sums
+
+// kWideStatsBatch: workgroup r sums record r's slot range
+// [begin * 4 + r, tileEnd[r] * 4 + r] (begin = tileEnd[r - 1], 0 for r = 0)
+// into stats[statIdx[r]].
+struct WideStatsBatchArgs {
+  const WideSlot* slots;
+  void* stats;                        // nbxWideStats*
+  uint32_t tileEnd[kListMaxRecs];
+  uint32_t statIdx[kListMaxRecs];
+};
+
 // Launch table for one element type of the collectives' fp32-accumulating
 // folds (nbx_wide_coll.h: the direct-schedule kernels of nbx_ll.h and
 // nbx_simple.h over FnWide). A table of its own, as WideSet: KernelSet and

@@ -21,6 +21,7 @@ namespace nbx {
 
 const KernelTable& table();       // nbx_reduce.cc
 const WideTable& wideTable();     // nbx_reduce_wide.cc
+const WideStatsTable& wideStatsTable();   // the STATS forms, same indices (nbx_reduce_wide.cc)
 int typeSize(int dt);             // bytes of an ncclDataType_t, -1 unknown (nbx_reduce.cc)
 
 // ---- launch policy, device and stream helpers (nbx_policy.cc) ----
@@ -87,7 +88,8 @@ enum LaunchFamily {
   kFamWideBatchList = 15,               // the same for nbxReduceMultiWideBatch (bit 1: fp32 output)
   kFamWideShiftedLds = 16               // wide realigning LDS-DMA (kWideShiftedLds)
 };
-enum LaunchFlag { kLaunchDynamic = 1, kLaunchOut32 = 2, kLaunchPartFirst = 4 };
+// kLaunchStats: the STATS form of a wide family (6 / 7 / 15 / 16) ran
+enum LaunchFlag { kLaunchDynamic = 1, kLaunchOut32 = 2, kLaunchPartFirst = 4, kLaunchStats = 8 };
 void logLaunch(int family, int nSrcs, int unroll, int flags);
 
 // Argument checks the batched entry points share with the single ones.
@@ -100,6 +102,18 @@ ncclResult_t checkBucket(size_t eb, size_t deb, bool apart, void* const* dsts, i
 enum WideLayout { kWideLayoutElts = 0, kWideLayoutPacks = 1, kWideLayoutShifted = 2 };
 int wideLayout(size_t eb, size_t deb, void* const* dsts, int nDsts, const void* const* srcs, int nSrcs, size_t count,
                size_t* head);
+// Bucket statistics (nbxReduceMultiWideStats). reduceMultiWideStats is
+// reduceMultiWideEx (nbx_internal.h) with a record to fill: the last pass runs
+// its STATS kernel into stream-ordered slot scratch, wideStatsFinish sums it.
+ncclResult_t reduceMultiWideStats(void* const* dsts, int nDsts, const void* const* srcs, int nSrcs, size_t count,
+                                  ncclDataType_t srcType, ncclDataType_t dstType, nbxDevRedOpFull op, int nPreOpSrcs,
+                                  ncclStream_t stream, int flags, nbxWideStats* stats);
+inline bool wideStatsPtrOk(const nbxWideStats* stats) { return stats != nullptr && ((uintptr_t)stats & 7u) == 0; }
+// Slot scratch for n slots and the upper levels of their tree (stream-ordered).
+WideSlot* wideStatsAlloc(size_t n, hipStream_t stream);
+// Sums slots[0 .. n) into *out (zeros for n = 0, slots may then be NULL) level
+// by level, then frees `slots` in stream order. Also frees after a failed launch.
+ncclResult_t wideStatsFinish(WideSlot* slots, size_t n, nbxWideStats* out, hipStream_t stream);
 // The op as the wide kernels take it: their scalar is an fp32 value, and only
 // PreMulSum has one — zero without it, the low 32 bits when passed by value.
 nbxDevRedOpFull wideScalarOp(nbxDevRedOpFull op);

@@ -230,9 +230,14 @@ bool batchListEnabled() { return g_batchMode.get() != 0; }
 // writer for both batched entry points: `kernel` is kReduceBatchList's or
 // kWideBatchList's instantiation for nSrcs, eb the sources' element size (the
 // head is counted in source elements), family / flagBits its launch record.
+// stats != nullptr (`kernel` is then kWideBatchListStats'): every launch gets
+// stream-ordered slot scratch — a slot per tile and wave and one per record,
+// nbx_wide.h "Bucket statistics" — as its second argument, and kWideStatsBatch
+// behind it sums record r's slots into stats[ts[r] - tasks].
 ncclResult_t launchBatchList(const void* kernel, int eb, int family, int flagBits, int nSrcs,
                              const std::vector<const nbxReduceTask*>& ts, const nbxDevRedOpFull& op, uint32_t mask,
-                             int postOp, int acq, hipStream_t st, size_t* done) {
+                             int postOp, int acq, hipStream_t st, size_t* done, const nbxReduceTask* tasks = nullptr,
+                             nbxWideStats* stats = nullptr) {
   *done = 0;
   const int dev = launchDevice(st);
   hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
@@ -291,9 +296,30 @@ ncclResult_t launchBatchList(const void* kernel, int eb, int family, int flagBit
     a.postOp = postOp;
     a.acquireSystem = acq;
     publishListSlot(dev, (const volatile uint32_t*)(recs + nRec * (size_t)recWords - 1));
-    void* args[] = {&a};
-    const hipError_t err = hipLaunchKernel(kernel, dim3((unsigned)G), dim3(kBlock), args, 0, st);
+    WideSlot* statSlots = nullptr;
+    if (stats != nullptr) {
+      statSlots = wideStatsAlloc(tiles * (kBlock / 64) + nRec, st);
+      if (statSlots == nullptr) {
+        releaseListSlot(dev, slot, st, nullptr, false);
+        return ncclUnhandledCudaError;
+      }
+    }
+    void* args[] = {&a, &statSlots};   // the plain kernels take the first alone
+    hipError_t err = hipLaunchKernel(kernel, dim3((unsigned)G), dim3(kBlock), args, 0, st);
     releaseListSlot(dev, slot, st, capturing ? graph : nullptr, err == hipSuccess);
+    if (err == hipSuccess && stats != nullptr) {
+      static_assert(sizeof(WideStatsBatchArgs) <= 4096, "the records' ranges must fit the kernel-argument segment");
+      WideStatsBatchArgs sa;
+      sa.slots = statSlots;
+      sa.stats = stats;
+      for (size_t r = 0; r < nRec; r++) {
+        sa.tileEnd[r] = a.tileEnd[r];
+        sa.statIdx[r] = (uint32_t)(ts[i + r] - tasks);
+      }
+      void* sargs[] = {&sa};
+      err = hipLaunchKernel(wideStatsKernels().batch, dim3((unsigned)nRec), dim3(kBlock), sargs, 0, st);
+    }
+    if (statSlots != nullptr && hipFreeAsync(statSlots, st) != hipSuccess && err == hipSuccess) err = hipErrorUnknown;
     if (err != hipSuccess) {
       std::fprintf(stderr, "nbx: batch-list kernel launch failed: %s\n", hipGetErrorString(err));
       return ncclUnhandledCudaError;
@@ -396,9 +422,11 @@ NBX_EXPORT ncclResult_t nbxReduceMultiBatch(const nbxReduceTask* tasks, int nTas
 // other bucket, and every bucket no table slot was left for, is one
 // nbxReduceMultiWide launch. There is no kernel-argument form, so batch modes
 // 1 and 2 both mean work lists.
-NBX_EXPORT ncclResult_t nbxReduceMultiWideBatch(const nbxReduceTask* tasks, int nTasks, ncclDataType_t srcType,
-                                                ncclDataType_t dstType, nbxDevRedOpFull op, int nPreOpSrcs,
-                                                ncclStream_t stream) {
+// stats != nullptr is nbxReduceMultiWideBatchStats: the STATS kernels, and
+// stats[k] for every bucket k — from its launch's slots, from the single call
+// where the bucket runs alone, zeros for an empty bucket.
+static ncclResult_t wideBatch(const nbxReduceTask* tasks, int nTasks, ncclDataType_t srcType, ncclDataType_t dstType,
+                              nbxDevRedOpFull op, int nPreOpSrcs, ncclStream_t stream, nbxWideStats* stats) {
   ncclResult_t r = checkWideOp(srcType, dstType, op);
   if (r != ncclSuccess) return r;
   if (nTasks < 0 || (nTasks > 0 && tasks == nullptr)) return ncclInvalidArgument;
@@ -413,10 +441,15 @@ NBX_EXPORT ncclResult_t nbxReduceMultiWideBatch(const nbxReduceTask* tasks, int 
     if (r != ncclSuccess) return r;
     any |= tasks[i].count != 0;
   }
-  if (!any) return ncclSuccess;
+  if (!any && stats == nullptr) return ncclSuccess;
   if (nPreOpSrcs < 0) nPreOpSrcs = 0;
   const bool pre = op.op == nbxDevPreMulSum;
   hipStream_t st = (hipStream_t)stream;
+  // a bucket as its own launch
+  auto alone = [&](const nbxReduceTask& t) {
+    return reduceMultiWideStats(t.dsts, t.nDsts, t.srcs, t.nSrcs, t.count, srcType, dstType, op, nPreOpSrcs, stream, 0,
+                                stats != nullptr ? stats + (&t - tasks) : nullptr);
+  };
   // single buckets first, in bucket order: layouts the pack kernel does not
   // take, > 8 sources (passes through the fp32 partial), everything under
   // launch variant 2, and buckets of 4+ sources whose body gives every CU an
@@ -426,38 +459,56 @@ NBX_EXPORT ncclResult_t nbxReduceMultiWideBatch(const nbxReduceTask* tasks, int 
   std::vector<const nbxReduceTask*> lists[kMaxKSrcs];
   for (int i = 0; i < nTasks; i++) {
     const nbxReduceTask& t = tasks[i];
-    if (t.count == 0) continue;
+    if (t.count == 0) {
+      if (stats != nullptr && (r = wideStatsFinish(nullptr, 0, stats + i, st)) != ncclSuccess) return r;
+      continue;
+    }
     size_t head = 0;
     const bool single = t.nSrcs > kMaxKSrcs || t.count > kBatchCountMask ||
                         wideLayout(eb, deb, t.dsts, t.nDsts, t.srcs, t.nSrcs, t.count, &head) != kWideLayoutPacks ||
                         bigTileRule(force, t.nSrcs, false, (t.count - head) / (16 / eb),
                                     (uint64_t)wideUnroll(t.nSrcs) * kBlock, cus, /*partialTileCounts=*/false);
     if (single) {
-      r = nbxReduceMultiWide(t.dsts, t.nDsts, t.srcs, t.nSrcs, t.count, srcType, dstType, op, nPreOpSrcs, stream);
+      r = alone(t);
       if (r != ncclSuccess) return r;
       continue;
     }
     lists[t.nSrcs - 1].push_back(&t);
   }
   const nbxDevRedOpFull lop = wideScalarOp(op);
+  const WideSet& lws = stats != nullptr ? wideStatsTable()[stype] : ws;
   const bool useList = batchListEnabled();
   for (int q = 0; q < kMaxKSrcs; q++) {
     if (lists[q].empty()) continue;
     const int ns = q + 1;
     size_t done = 0;
     if (useList) {
-      r = launchBatchList(ws.batchList[out32 ? 1 : 0][q], (int)eb, kFamWideBatchList, out32 ? kLaunchOut32 : 0, ns,
-                          lists[q], lop, preMask(pre, nPreOpSrcs, 0, ns, 0), 0, 0, st, &done);
+      r = launchBatchList(lws.batchList[out32 ? 1 : 0][q], (int)eb, kFamWideBatchList,
+                          (out32 ? kLaunchOut32 : 0) | (stats != nullptr ? kLaunchStats : 0), ns, lists[q], lop,
+                          preMask(pre, nPreOpSrcs, 0, ns, 0), 0, 0, st, &done, tasks, stats);
       if (r != ncclSuccess) return r;
     }
     // the rest one launch each (work lists off, or no table slot free)
     for (size_t j = done; j < lists[q].size(); j++) {
-      const nbxReduceTask& t = *lists[q][j];
-      r = nbxReduceMultiWide(t.dsts, t.nDsts, t.srcs, t.nSrcs, t.count, srcType, dstType, op, nPreOpSrcs, stream);
+      r = alone(*lists[q][j]);
       if (r != ncclSuccess) return r;
     }
   }
   return ncclSuccess;
+}
+
+NBX_EXPORT ncclResult_t nbxReduceMultiWideBatch(const nbxReduceTask* tasks, int nTasks, ncclDataType_t srcType,
+                                                ncclDataType_t dstType, nbxDevRedOpFull op, int nPreOpSrcs,
+                                                ncclStream_t stream) {
+  return wideBatch(tasks, nTasks, srcType, dstType, op, nPreOpSrcs, stream, nullptr);
+}
+
+NBX_EXPORT ncclResult_t nbxReduceMultiWideBatchStats(const nbxReduceTask* tasks, int nTasks, ncclDataType_t srcType,
+                                                     ncclDataType_t dstType, nbxDevRedOpFull op, int nPreOpSrcs,
+                                                     nbxWideStats* stats, ncclStream_t stream) {
+  if (nTasks > 0 && !wideStatsPtrOk(stats)) return ncclInvalidArgument;
+  if (nTasks <= 0) stats = nullptr;   // nothing to write
+  return wideBatch(tasks, nTasks, srcType, dstType, op, nPreOpSrcs, stream, stats);
 }
 
 NBX_EXPORT int nbxDebugSetBatchMode(int mode) { return g_batchMode.set(mode, mode >= 0 && mode <= 2); }

@@ -12,6 +12,8 @@ namespace {
 // their own table, so nbxKernelCount and KernelSet stay as they are
 WideTable g_wide;
 std::once_flag g_wideOnce;
+WideStatsTable g_wideStats;
+std::once_flag g_wideStatsOnce;
 
 // Elements from which a call outside the pack layout takes the realigning
 // kernel (kWideShiftedLds) instead of the element kernel; env
@@ -38,17 +40,32 @@ LazySetting<long long> g_wideShiftMinElts{0, parseWideShiftMinElts};
 // layout / head are decided once per call from the caller's pointers (every
 // pass of a call folds sources of the same alignment into the same partial).
 // op: as wideScalarOp() returns it.
+// stats != nullptr (a call's last pass): `ws` is the STATS table's set, the
+// kernel takes slot scratch sized by the pass's tiles as its second argument,
+// and wideStatsFinish sums it into *stats. The tile shapes, and with them the
+// slots, are the plain launch's; only the element kernel is cut into tiles
+// (kWideEltsStatTile) where the plain one strides.
 ncclResult_t launchWidePass(const WideSet& ws, bool out32, bool partFirst, int layout, size_t head, void* const* dsts,
                             int nDsts, const void* const* srcs, int nSrcs, size_t count, const nbxDevRedOpFull& op,
-                            uint32_t mask, int acquireSystem, hipStream_t stream) {
+                            uint32_t mask, int acquireSystem, hipStream_t stream, nbxWideStats* stats = nullptr) {
   KArgs a;
   fillKArgs(a, dsts, nDsts, srcs, nSrcs, count, op, mask);
   a.acquireSystem = acquireSystem;
   const int dev = launchDevice(stream);
   const size_t cus = (size_t)cuCount(dev);
-  void* args[] = {&a};
+  WideSlot* slots = nullptr;
+  size_t nSlots = 0;
+  void* args[] = {&a, &slots};   // the plain kernels take the first alone
   hipError_t err;
-  const int wideFlags = (out32 ? kLaunchOut32 : 0) | (partFirst ? kLaunchPartFirst : 0);
+  const int wideFlags =
+      (out32 ? kLaunchOut32 : 0) | (partFirst ? kLaunchPartFirst : 0) | (stats != nullptr ? kLaunchStats : 0);
+  // a slot per tile and wave plus the head and tail elements' (pack and realigning kernels)
+  auto statSlots = [&](size_t n) {
+    if (stats == nullptr) return true;
+    nSlots = n;
+    slots = wideStatsAlloc(n, stream);
+    return slots != nullptr;
+  };
   const int o = out32 ? 1 : 0, p = partFirst ? 1 : 0;
   Body b(count, head, 16 / ws.eltBytes);
   if (layout == kWideLayoutPacks) {
@@ -59,6 +76,7 @@ ncclResult_t launchWidePass(const WideSet& ws, bool out32, bool partFirst, int l
     b.cut((size_t)unroll * kBlock, cus * (size_t)perCU);
     b.into(a);
     a.variant = big ? 1 : 0;
+    if (!statSlots(b.tiles * (kBlock / 64) + 1)) return ncclUnhandledCudaError;
     // dynamic tiles under launchPass's rule: unrolled tiles, long launches
     DynLaunch dyn;
     if (big && b.tiles >= (size_t)dynMinTilesPerWG() * b.grid) dyn.begin(dev, stream, b.tiles, a);
@@ -72,20 +90,24 @@ ncclResult_t launchWidePass(const WideSet& ws, bool out32, bool partFirst, int l
     const int unroll = shiftLdsUnroll(nSrcs);
     b.cut((size_t)unroll * 64 * kShiftLdsWaves, cus * (size_t)shiftedBlocksPerCU(true, nSrcs));
     b.into(a);
+    if (!statSlots(b.tilesOf((size_t)unroll * 64) + 1)) return ncclUnhandledCudaError;   // per wave tile
     err = hipLaunchKernel(ws.shiftedLds[o][p][nSrcs - 1], dim3((unsigned)b.grid),
                           dim3((unsigned)(kShiftLdsWaves * 64)), args, 0, stream);
     logLaunch(kFamWideShiftedLds, nSrcs, unroll, wideFlags);
   } else {
-    const size_t blocks = (count + kBlock - 1) / kBlock;
+    const size_t perBlock = stats != nullptr ? (size_t)kWideEltsStatTile * kBlock : (size_t)kBlock;
+    const size_t blocks = (count + perBlock - 1) / perBlock;
+    if (!statSlots(blocks * (kBlock / 64))) return ncclUnhandledCudaError;
     const size_t grid = cappedGrid(blocks, cus * (size_t)maxBlocksPerCU(false, nSrcs, /*classic=*/true));
     err = hipLaunchKernel(ws.elts[o][p], dim3((unsigned)grid), dim3(kBlock), args, 0, stream);
     logLaunch(kFamWideElts, nSrcs, 1, wideFlags);
   }
   if (err != hipSuccess) {
     std::fprintf(stderr, "nbx: wide kernel launch failed: %s\n", hipGetErrorString(err));
+    if (slots != nullptr) (void)hipFreeAsync(slots, stream);
     return ncclUnhandledCudaError;
   }
-  return ncclSuccess;
+  return stats != nullptr ? wideStatsFinish(slots, nSlots, stats, stream) : ncclSuccess;
 }
 
 // Pack-kernel layout: the sources share one misalignment modulo 16, and behind
@@ -108,6 +130,48 @@ const WideTable& wideTable() {
     fillWide(g_wide);
   });
   return g_wide;
+}
+
+const WideStatsTable& wideStatsTable() {
+  std::call_once(g_wideStatsOnce, [] {
+    std::memset(&g_wideStats, 0, sizeof(g_wideStats));
+    fillWideStats(g_wideStats);
+  });
+  return g_wideStats;
+}
+
+// n slots, then the slots of every upper level of the tree: ceil(n / fan), ...
+// down to the level one workgroup sums (fewer than n / (fan - 1) + 4 in all:
+// each level rounds up once, and at most two levels are stored below 2^36 slots).
+WideSlot* wideStatsAlloc(size_t n, hipStream_t stream) {
+  void* p = nullptr;
+  const size_t total = n + n / (size_t)(kWideStatsFan - 1) + 4;
+  if (hipMallocAsync(&p, total * sizeof(WideSlot), stream) != hipSuccess) return nullptr;
+  return (WideSlot*)p;
+}
+
+ncclResult_t wideStatsFinish(WideSlot* slots, size_t n, nbxWideStats* out, hipStream_t stream) {
+  const void* kernel = wideStatsKernels().reduce;
+  const WideSlot* in = slots;
+  hipError_t err = hipSuccess;
+  for (;;) {
+    const bool last = n <= (size_t)kWideStatsFan;
+    uint64_t n64 = n;
+    const size_t groups = last ? 1 : (n + kWideStatsFan - 1) / kWideStatsFan;
+    WideSlot* next = last ? nullptr : const_cast<WideSlot*>(in) + n;
+    nbxWideStats* o = last ? out : nullptr;
+    void* args[] = {&in, &n64, &next, &o};
+    err = hipLaunchKernel(kernel, dim3((unsigned)groups), dim3(kBlock), args, 0, stream);
+    if (err != hipSuccess || last) break;
+    in = next;
+    n = groups;
+  }
+  if (slots != nullptr && hipFreeAsync(slots, stream) != hipSuccess && err == hipSuccess) err = hipErrorUnknown;
+  if (err != hipSuccess) {
+    std::fprintf(stderr, "nbx: wide statistics kernel launch failed: %s\n", hipGetErrorString(err));
+    return ncclUnhandledCudaError;
+  }
+  return ncclSuccess;
 }
 
 nbxDevRedOpFull wideScalarOp(nbxDevRedOpFull op) {
@@ -151,14 +215,25 @@ int wideLayout(size_t eb, size_t deb, void* const* dsts, int nDsts, const void* 
 ncclResult_t reduceMultiWideEx(void* const* dsts, int nDsts, const void* const* srcs, int nSrcs, size_t count,
                                ncclDataType_t srcType, ncclDataType_t dstType, nbxDevRedOpFull op, int nPreOpSrcs,
                                ncclStream_t stream, int flags) {
+  return reduceMultiWideStats(dsts, nDsts, srcs, nSrcs, count, srcType, dstType, op, nPreOpSrcs, stream, flags,
+                              nullptr);
+}
+
+// stats != nullptr (checked by the caller): the call's last pass takes its
+// STATS kernel; the passes before it are the plain ones, so nothing of the
+// intermediate partial reaches the record.
+ncclResult_t reduceMultiWideStats(void* const* dsts, int nDsts, const void* const* srcs, int nSrcs, size_t count,
+                                  ncclDataType_t srcType, ncclDataType_t dstType, nbxDevRedOpFull op, int nPreOpSrcs,
+                                  ncclStream_t stream, int flags, nbxWideStats* stats) {
   const int acq = (flags & kReduceAcquireSystem) ? 1 : 0;
   if (!argArraysOk(dsts, nDsts, srcs, nSrcs)) return ncclInvalidArgument;
   ncclResult_t cr = checkWideOp(srcType, dstType, op);
   if (cr != ncclSuccess) return cr;
-  if (count == 0) return ncclSuccess;
+  if (count == 0) return stats != nullptr ? wideStatsFinish(nullptr, 0, stats, (hipStream_t)stream) : ncclSuccess;
   const int st = (int)srcType;
   const bool pre = op.op == nbxDevPreMulSum;
   const WideSet& ws = wideTable()[st];
+  const WideSet& lastWs = stats != nullptr ? wideStatsTable()[st] : ws;
   const bool out32 = (int)dstType != st;
   const size_t eb = (size_t)ws.eltBytes, deb = out32 ? sizeof(float) : eb;
   cr = checkBucket(eb, deb, out32, dsts, nDsts, srcs, nSrcs, count);
@@ -171,8 +246,8 @@ ncclResult_t reduceMultiWideEx(void* const* dsts, int nDsts, const void* const* 
   const int layout = wideLayout(eb, deb, dsts, nDsts, srcs, nSrcs, count, &head);
 
   if (nSrcs <= kMaxKSrcs)
-    return launchWidePass(ws, out32, false, layout, head, dsts, nDsts, srcs, nSrcs, count, lop,
-                          preMask(pre, nPreOpSrcs, 0, nSrcs, 0), acq, strm);
+    return launchWidePass(lastWs, out32, false, layout, head, dsts, nDsts, srcs, nSrcs, count, lop,
+                          preMask(pre, nPreOpSrcs, 0, nSrcs, 0), acq, strm, stats);
 
   // > 8 sources (foldPasses) through an fp32 partial that is never narrowed,
   // so the result is the single fp32 left fold. The partial lives in dsts[0]
@@ -190,8 +265,9 @@ ncclResult_t reduceMultiWideEx(void* const* dsts, int nDsts, const void* const* 
   return foldPasses(dsts, nDsts, srcs, nSrcs, part, scratch, strm,
                     [&](void* const* d, int nd, const void* const* s, int n, int first, bool partFirst, bool last) {
                       const int slot0 = partFirst ? 1 : 0;
-                      return launchWidePass(ws, last ? out32 : true, partFirst, layout, head, d, nd, s, n, count, lop,
-                                            preMask(pre, nPreOpSrcs, first, n - slot0, slot0), acq, strm);
+                      return launchWidePass(last ? lastWs : ws, last ? out32 : true, partFirst, layout, head, d, nd,
+                                            s, n, count, lop, preMask(pre, nPreOpSrcs, first, n - slot0, slot0), acq,
+                                            strm, last ? stats : nullptr);
                     });
 }
 
@@ -203,6 +279,14 @@ NBX_EXPORT ncclResult_t nbxReduceMultiWide(void* const* dsts, int nDsts, const v
                                            size_t count, ncclDataType_t srcType, ncclDataType_t dstType,
                                            nbxDevRedOpFull op, int nPreOpSrcs, ncclStream_t stream) {
   return reduceMultiWideEx(dsts, nDsts, srcs, nSrcs, count, srcType, dstType, op, nPreOpSrcs, stream, 0);
+}
+
+NBX_EXPORT ncclResult_t nbxReduceMultiWideStats(void* const* dsts, int nDsts, const void* const* srcs, int nSrcs,
+                                                size_t count, ncclDataType_t srcType, ncclDataType_t dstType,
+                                                nbxDevRedOpFull op, int nPreOpSrcs, nbxWideStats* stats,
+                                                ncclStream_t stream) {
+  if (!wideStatsPtrOk(stats)) return ncclInvalidArgument;
+  return reduceMultiWideStats(dsts, nDsts, srcs, nSrcs, count, srcType, dstType, op, nPreOpSrcs, stream, 0, stats);
 }
 
 NBX_EXPORT long long nbxDebugSetWideShiftMinElts(long long elts) { return g_wideShiftMinElts.set(elts, elts >= 1); }

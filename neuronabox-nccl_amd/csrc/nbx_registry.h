@@ -29,6 +29,21 @@ void fillWide(WideTable& t);
 void fillWideShift16(WideTable& t);
 void fillWideShift8(WideTable& t);
 
+// their STATS forms (nbxReduceMultiWideStats): a table of its own with the
+// same indices, a unit per element width and kernel family
+// (inst_wide_stats*.hip), and the two kernels that sum the slots
+typedef WideSet WideStatsTable[kNumTypes];
+void fillWideStats(WideStatsTable& t);   // inst_wide_stats_sum.hip; calls the four below
+void fillWideStats16(WideStatsTable& t);
+void fillWideStats8(WideStatsTable& t);
+void fillWideStatsShift16(WideStatsTable& t);
+void fillWideStatsShift8(WideStatsTable& t);
+struct WideStatsKernels {
+  const void* reduce;   // kWideStatsReduce
+  const void* batch;    // kWideStatsBatch
+};
+WideStatsKernels wideStatsKernels();
+
 // the collectives' fp32-accumulating kernels: one WideCollSet per element
 // type, a unit per element width (inst_wide_coll*.hip)
 typedef WideCollSet WideCollTable[kNumTypes];

@@ -27,6 +27,10 @@
 // result is the single fp32 left fold over all sources).
 // A third family, kWideBatchList<W, NSRC, OUT32>, runs many buckets from a
 // work-list table in one launch (nbxReduceMultiWideBatch; below).
+// Every kernel has a STATS form (k...Stats, nbxReduceMultiWideStats): the same
+// body with the bucket statistics of the final accumulators folded in
+// ("Bucket statistics" below). A plain kernel and its STATS form share their
+// body as text (nbx_wide_*.inc), and the plain kernels are what they were.
 #pragma once
 #include "nbx_kernels.h"   // ldPack / stPack, forEachTile
 
@@ -95,9 +99,62 @@ __device__ __forceinline__ float loadWideArg(const void* argPtr, uint64_t arg) {
   return argPtr != nullptr ? *(const float*)argPtr : __uint_as_float((uint32_t)arg);
 }
 
+// ---------------------------------------------------------------------------
+// Bucket statistics (nbxReduceMultiWideStats): amax = max |acc| and sumSq =
+// sum acc^2 over the final fp32 accumulators, taken where they sit in
+// registers. A lane keeps two fp32 square-sums (one per half of an accumulator
+// pair, one fma per element: one rounding) and one fp32 running max for the
+// duration of ONE tile; at the tile's end the two sums are widened to fp64 and
+// added, the wave folds sum and max over a fixed xor butterfly (fp64 adds are
+// commutative, so every lane ends on the same bits) and lane 0 stores one
+// 16-byte WideSlot at an index that depends on the tile and the wave alone:
+//   pack kernel       tile * 4 + wave; head and tail elements: nTiles * 4
+//   realigning kernel wave tile; head and tail elements: nTiles
+//   element kernel    tile * 4 + wave, a tile being kWideEltsStatTile x kBlock elements
+//   batch kernel      tile * 4 + k + wave for global tile `tile` of record k;
+//                     record k's head and tail elements: tileEnd[k] * 4 + k
+// Every slot of the range is written exactly once (zeros by a wave with no
+// element), by whichever workgroup ran the tile: no LDS, no barrier, no
+// atomic, and nothing depends on the grid or the tile schedule. kWideStatsReduce
+// / kWideStatsBatch (inst_wide_stats_sum.hip) sum the slots in a fixed tree.
+// IEEE max drops a NaN, the square-sum keeps it (every term is >= 0 or NaN, so
+// no inf - inf): the final kernel reports amax = NaN exactly when sumSq is.
+// fp32 roundings into one fp64 partial: packs per lane per tile x kEPP / 2 —
+// at most 4 x 8 = 32 (fp8 from 4 sources); include/nbx_reduce.h states it.
+struct WideLaneStats {
+  f32x2 sq;
+  float mx;
+  __device__ __forceinline__ void reset() {
+    sq = f32x2{0.0f, 0.0f};
+    mx = 0.0f;
+  }
+  __device__ __forceinline__ void add(const f32x2& a) {
+    sq[0] = __builtin_fmaf(a[0], a[0], sq[0]);
+    sq[1] = __builtin_fmaf(a[1], a[1], sq[1]);
+    mx = __builtin_fmaxf(mx, __builtin_fmaxf(__builtin_fabsf(a[0]), __builtin_fabsf(a[1])));   // v_max3_f32 |a0|, |a1|
+  }
+  __device__ __forceinline__ void add(float a) {
+    sq[0] = __builtin_fmaf(a, a, sq[0]);
+    mx = __builtin_fmaxf(mx, __builtin_fabsf(a));
+  }
+};
+
+// End of a tile: called by all 64 lanes of the wave, converged.
+__device__ __forceinline__ void wideStatsFlush(WideLaneStats& ls, WideSlot* slot) {
+  double s = (double)ls.sq[0] + (double)ls.sq[1];
+  float m = ls.mx;
+#pragma unroll
+  for (int o = 32; o >= 1; o >>= 1) {
+    s = s + __shfl_xor(s, o, 64);
+    m = __builtin_fmaxf(m, __shfl_xor(m, o, 64));
+  }
+  if ((threadIdx.x & 63u) == 0) *slot = WideSlot{s, m, 0u};
+  ls.reset();
+}
+
 // One element, any source count <= kMaxKSrcs (uniform guards, as reduceElt).
-template <class W, bool OUT32, bool PART>
-__device__ __forceinline__ void wideElt(const KArgs& a, float sc, int nSrcs, uint64_t i) {
+template <class W, bool OUT32, bool PART, bool STATS = false>
+__device__ __forceinline__ void wideElt(const KArgs& a, float sc, int nSrcs, uint64_t i, WideLaneStats* ls = nullptr) {
   using E = typename W::Elt;
   float acc;
   if constexpr (PART) {
@@ -114,6 +171,7 @@ __device__ __forceinline__ void wideElt(const KArgs& a, float sc, int nSrcs, uin
       acc = acc + v;
     }
   }
+  if constexpr (STATS) ls->add(acc);
 #pragma unroll
   for (int d = 0; d < kMaxKDsts; d++) {
     if (d < a.nDsts) {
@@ -137,10 +195,11 @@ __device__ __forceinline__ void widePack(const u32x4& v, f32x2 (&f)[W::kEPP / 2]
 // multiply per element whatever the mask, and no multiply at all in the
 // plain sum (a per-source test of the mask inside the fold compiled into a
 // multiply AND a select per element for every source).
-template <class W, int NSRC, int U, bool OUT32, bool PART, bool PRE>
+// STATS: the final accumulators also go into *ls.
+template <class W, int NSRC, int U, bool OUT32, bool PART, bool PRE, bool STATS = false>
 __device__ __forceinline__ void wideFoldStore(const u32x4 (&part)[U][W::kEPP / 4], const u32x4 (&v)[NSRC][U],
                                               const float (&mul)[NSRC], u32x4* const (&dst)[kMaxKDsts], int nDsts,
-                                              uint64_t p) {
+                                              uint64_t p, WideLaneStats* ls = nullptr) {
   constexpr int NP = W::kEPP / 2;   // fp32 pairs per pack
   constexpr int Q = W::kEPP / 4;    // dwordx4 per pack of fp32
 #pragma unroll
@@ -171,6 +230,10 @@ __device__ __forceinline__ void wideFoldStore(const u32x4 (&part)[U][W::kEPP / 4
       }
 #pragma unroll
       for (int k = 0; k < NP; k++) acc[k] = acc[k] + t[k];
+    }
+    if constexpr (STATS) {
+#pragma unroll
+      for (int k = 0; k < NP; k++) ls->add(acc[k]);
     }
     const uint64_t q = p + (uint64_t)u * kBlock;
     if constexpr (OUT32) {
@@ -212,62 +275,38 @@ __device__ __forceinline__ void wideLoadTile(u32x4 (&part)[U][W::kEPP / 4], u32x
     for (int u = 0; u < U; u++) v[s][u] = ldPack(src[s] + p + (uint64_t)u * kBlock);
 }
 
+// The helper calls of a shared body: the plain kernel's is the call it always
+// made, the STATS kernel's passes the lane's statistics as the last argument.
+#define NBX_WIDE_FOLD(U_, PART_, PRE_, ...)                                                       \
+  do {                                                                                            \
+    if constexpr (STATS) wideFoldStore<W, NSRC, U_, OUT32, PART_, PRE_, true>(__VA_ARGS__, &ls);  \
+    else wideFoldStore<W, NSRC, U_, OUT32, PART_, PRE_>(__VA_ARGS__);                             \
+  } while (0)
+#define NBX_WIDE_ELT(...)                                                  \
+  do {                                                                     \
+    if constexpr (STATS) wideElt<W, OUT32, PART, true>(__VA_ARGS__, &ls);  \
+    else wideElt<W, OUT32, PART>(__VA_ARGS__);                             \
+  } while (0)
+#define NBX_WIDE_BATCH_ELT(...)                                                 \
+  do {                                                                          \
+    if constexpr (STATS) wideBatchElt<W, NSRC, OUT32, true>(__VA_ARGS__, &ls);  \
+    else wideBatchElt<W, NSRC, OUT32>(__VA_ARGS__);                             \
+  } while (0)
+
+// The body is text shared by the plain and the STATS kernel
+// (nbx_wide_packs.inc: it reads `a`, `slots` and the constant STATS), so that
+// the plain kernel keeps reading its own kernel argument, as it always did.
 template <class W, int NSRC, int U, bool OUT32, bool PART>
 __global__ __launch_bounds__(kBlock) void kWidePacks(KArgs a) {
-  using E = typename W::Elt;
-  constexpr int EPP = W::kEPP, Q = EPP / 4;
-  static_assert(!PART || NSRC >= 2, "a pass that reads a partial folds at least one more source");
-  acquirePeerData(a);   // a clique's fold reads its peers' buffers (reduceMultiWideEx)
-  const float sc = loadWideArg(a.argPtr, a.arg);
-  const uint64_t head = (uint64_t)a.headElts;
-  const u32x4* src[NSRC];
-#pragma unroll
-  for (int s = 0; s < NSRC; s++)
-    src[s] = (const u32x4*)((const char*)a.src[s] + head * (PART && s == 0 ? sizeof(float) : sizeof(E)));
-  u32x4* dst[kMaxKDsts];
-#pragma unroll
-  for (int d = 0; d < kMaxKDsts; d++) dst[d] = (u32x4*)((char*)a.dst[d] + head * (OUT32 ? sizeof(float) : sizeof(E)));
-  const int nDsts = a.nDsts;
-  const bool pre = a.preMask != 0;   // uniform: the fold is chosen per tile, never per element
-  float mul[NSRC];
-#pragma unroll
-  for (int s = 0; s < NSRC; s++) mul[s] = ((a.preMask >> s) & 1u) ? sc : 1.0f;
-  const uint64_t n = a.nPacks;
-  constexpr uint64_t kTile = (uint64_t)U * kBlock;
-  forEachTile(a, (n + kTile - 1) / kTile, [&](uint64_t t) {
-    const uint64_t p = t * kTile + threadIdx.x;
-    if (p + (uint64_t)(U - 1) * kBlock < n) {
-      // full tile: issue every load first, then fold
-      u32x4 part[U][Q];
-      u32x4 v[NSRC][U];
-      wideLoadTile<W, NSRC, U, PART>(part, v, src, p);
-      __builtin_amdgcn_sched_barrier(0);
-      if (pre) wideFoldStore<W, NSRC, U, OUT32, PART, true>(part, v, mul, dst, nDsts, p);
-      else wideFoldStore<W, NSRC, U, OUT32, PART, false>(part, v, mul, dst, nDsts, p);
-    } else {
-      // last, partial tile
-#pragma unroll
-      for (int u = 0; u < U; u++) {
-        const uint64_t q = p + (uint64_t)u * kBlock;
-        if (q < n) {
-          u32x4 part1[1][Q];
-          u32x4 v1[NSRC][1];
-          wideLoadTile<W, NSRC, 1, PART>(part1, v1, src, q);
-          wideFoldStore<W, NSRC, 1, OUT32, PART, true>(part1, v1, mul, dst, nDsts, q);
-        }
-      }
-    }
-  });
+  constexpr bool STATS = false;
+  WideSlot* const slots = nullptr;
+#include "nbx_wide_packs.inc"
+}
 
-  // head (< EPP elements before the aligned body) and tail (< EPP after it)
-  if (blockIdx.x == gridDim.x - 1) {
-    const int h = a.headElts;
-    const uint64_t tailStart = head + n * EPP;
-    const int tail = (int)(a.nElts - tailStart);
-    const int t = (int)threadIdx.x;
-    if (t < h) wideElt<W, OUT32, PART>(a, sc, NSRC, (uint64_t)t);
-    else if (t < h + tail) wideElt<W, OUT32, PART>(a, sc, NSRC, tailStart + (uint64_t)(t - h));
-  }
+template <class W, int NSRC, int U, bool OUT32, bool PART>
+__global__ __launch_bounds__(kBlock) void kWidePacksStats(KArgs a, WideSlot* slots) {
+  constexpr bool STATS = true;
+#include "nbx_wide_packs.inc"
 }
 
 // Element kernel: sources on different alignments modulo 16, or a destination
@@ -279,6 +318,27 @@ __global__ __launch_bounds__(kBlock) void kWideElts(KArgs a) {
   const uint64_t stride = (uint64_t)gridDim.x * kBlock;
   for (uint64_t i = (uint64_t)blockIdx.x * kBlock + threadIdx.x; i < a.nElts; i += stride)
     wideElt<W, OUT32, PART>(a, sc, a.nSrcs, i);
+}
+
+// Its STATS form: tiles of kWideEltsStatTile x kBlock elements whatever the
+// grid is, one slot per tile and wave (kWideEltsStatTile = 8 fp32 roundings
+// into a slot's fp64 partial: one square-sum chain per lane).
+template <class W, bool OUT32, bool PART>
+__global__ __launch_bounds__(kBlock) void kWideEltsStats(KArgs a, WideSlot* slots) {
+  acquirePeerData(a);
+  const float sc = loadWideArg(a.argPtr, a.arg);
+  constexpr uint64_t kTile = (uint64_t)kWideEltsStatTile * kBlock;
+  const uint64_t nTiles = (a.nElts + kTile - 1) / kTile;
+  WideLaneStats ls;
+  ls.reset();
+  for (uint64_t t = blockIdx.x; t < nTiles; t += gridDim.x) {
+#pragma unroll
+    for (int j = 0; j < kWideEltsStatTile; j++) {
+      const uint64_t i = t * kTile + (uint64_t)j * kBlock + threadIdx.x;
+      if (i < a.nElts) wideElt<W, OUT32, PART, true>(a, sc, a.nSrcs, i, &ls);
+    }
+    wideStatsFlush(ls, slots + t * (kBlock / 64) + (threadIdx.x >> 6));
+  }
 }
 
 // Realigning kernel: kReduceShiftedLds' staging (nbx_kernels.h — the typed
@@ -299,125 +359,15 @@ __global__ __launch_bounds__(kBlock) void kWideElts(KArgs a) {
 // no DMA is issued at all.
 template <class W, int NSRC, bool OUT32, bool PART>
 __global__ __launch_bounds__(kShiftLdsWaves * 64) void kWideShiftedLds(KArgs a) {
-  using E = typename W::Elt;
-  constexpr int EPP = W::kEPP, Q = EPP / 4;
-  static_assert(!PART || NSRC >= 2, "a pass that reads a partial folds at least one more source");
-  static_assert(kShiftLdsWaves * 64 == kBlock, "the head and tail elements count on kBlock lanes");
-  constexpr int F = PART ? 1 : 0;   // first staged source
-  constexpr int NST = NSRC - F;     // staged sources
-  constexpr int U = shiftLdsUnroll(NSRC), S = kShiftLdsStages, WV = kShiftLdsWaves;
-  constexpr int P = U * 64 + 1;     // packs per source per stage
-  constexpr uint64_t kTile = (uint64_t)U * 64;
-  __shared__ u32x4 sm[WV][S][NST][P];
-  acquirePeerData(a);
-  const float sc = loadWideArg(a.argPtr, a.arg);
-  const uint64_t head = (uint64_t)a.headElts;
-  const uint64_t n = a.nPacks;
-  const u32x4* base[NSRC];
-  uint32_t sh[NSRC];
-  uint64_t lim[NSRC];
-#pragma unroll
-  for (int s = F; s < NSRC; s++) {
-    alignDown16((uintptr_t)a.src[s] + head * sizeof(E), base[s], sh[s]);
-    lim[s] = sh[s] ? n : (n ? n - 1 : 0);
-  }
-  const u32x4* partial = (const u32x4*)((const char*)a.src[0] + head * sizeof(float));   // PART only
-  u32x4* dst[kMaxKDsts];
-#pragma unroll
-  for (int d = 0; d < kMaxKDsts; d++) dst[d] = (u32x4*)((char*)a.dst[d] + head * (OUT32 ? sizeof(float) : sizeof(E)));
-  const int nDsts = a.nDsts;
-  const bool pre = a.preMask != 0;   // uniform: the fold is chosen per tile, never per element
-  float mul[NSRC];
-#pragma unroll
-  for (int s = 0; s < NSRC; s++) mul[s] = ((a.preMask >> s) & 1u) ? sc : 1.0f;
-  const int wave = (int)(threadIdx.x >> 6), lane = (int)(threadIdx.x & 63u);
-  const uint64_t nTiles = (n + kTile - 1) / kTile;
-  const uint64_t nWaves = (uint64_t)gridDim.x * WV, gw = (uint64_t)blockIdx.x * WV + (uint64_t)wave;
-  auto issue = [&](uint64_t t, int st) {
-    const uint64_t p0 = t * kTile;
-#pragma unroll
-    for (int s = F; s < NSRC; s++) {
-#pragma unroll
-      for (int u = 0; u < U; u++) {
-        const uint64_t q = p0 + (uint64_t)(u * 64 + lane);
-        __builtin_amdgcn_global_load_lds((const void*)(base[s] + (q < lim[s] ? q : lim[s])),
-                                         (__attribute__((address_space(3))) void*)&sm[wave][st][s - F][u * 64], 16, 0,
-                                         2 /* nt */);
-      }
-      if (lane == 0) {
-        const uint64_t q = p0 + kTile;
-        __builtin_amdgcn_global_load_lds((const void*)(base[s] + (q < lim[s] ? q : lim[s])),
-                                         (__attribute__((address_space(3))) void*)&sm[wave][st][s - F][kTile], 16, 0,
-                                         2);
-      }
-    }
-  };
-  // the fp32 partial of wave tile t (lanes past the body read its last pack)
-  auto loadPart = [&](uint64_t t, u32x4 (&part)[U][Q]) {
-    if constexpr (PART) {
-#pragma unroll
-      for (int u = 0; u < U; u++) {
-        const uint64_t q = t * kTile + (uint64_t)(u * 64 + lane);
-        const uint64_t qc = q < n ? q : n - 1;
-#pragma unroll
-        for (int j = 0; j < Q; j++) part[u][j] = ldPack(partial + qc * Q + j);
-      }
-    }
-  };
-  // fold wave tile t from stage st (its DMA has landed) and store it
-  auto foldTile = [&](uint64_t t, int st, const u32x4 (&part)[U][Q]) {
-#pragma unroll
-    for (int u = 0; u < U; u++) {
-      const uint64_t q = t * kTile + (uint64_t)(u * 64 + lane);
-      if (q < n) {
-        u32x4 part1[1][Q];
-        u32x4 v1[NSRC][1];
-        if constexpr (PART) {
-#pragma unroll
-          for (int j = 0; j < Q; j++) part1[0][j] = part[u][j];
-        }
-#pragma unroll
-        for (int s = F; s < NSRC; s++) {
-          v1[s][0] = stageRead(&sm[wave][st][s - F][0], sh[s], (uint32_t)(u * 64 + lane));
-        }
-        if (pre) wideFoldStore<W, NSRC, 1, OUT32, PART, true>(part1, v1, mul, dst, nDsts, q);
-        else wideFoldStore<W, NSRC, 1, OUT32, PART, false>(part1, v1, mul, dst, nDsts, q);
-      }
-    }
-    // this stage's LDS reads have returned before a later iteration refills it
-    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-  };
-#pragma unroll
-  for (int k = 0; k < S - 1; k++) {
-    const uint64_t t = gw + (uint64_t)k * nWaves;
-    if (t < nTiles) issue(t, k);
-  }
-  int st = 0;
-  for (uint64_t t = gw; t < nTiles; t += nWaves) {
-    u32x4 part[U][Q];
-    loadPart(t, part);
-    if (t + (uint64_t)(S - 1) * nWaves < nTiles) {
-      issue(t + (uint64_t)(S - 1) * nWaves, (st + S - 1) % S);
-      // everything but the newer tiles' DMA (NST x (U + 1) instructions each)
-      // has landed: this tile's DMA and its partial; stores counted in vmcnt
-      // only make the wait stricter
-      asm volatile("s_waitcnt vmcnt(%0)" ::"n"((S - 1) * NST * (U + 1)) : "memory");
-    } else {
-      asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    }
-    foldTile(t, st, part);
-    st = st + 1 == S ? 0 : st + 1;
-  }
+  constexpr bool STATS = false;
+  WideSlot* const slots = nullptr;
+#include "nbx_wide_shifted.inc"
+}
 
-  // head (before the destinations' 16-B boundary) and tail elements
-  if (blockIdx.x == gridDim.x - 1) {
-    const int h = a.headElts;
-    const uint64_t tailStart = head + n * EPP;
-    const int tail = (int)(a.nElts - tailStart);
-    const int th = (int)threadIdx.x;
-    if (th < h) wideElt<W, OUT32, PART>(a, sc, NSRC, (uint64_t)th);
-    else if (th < h + tail) wideElt<W, OUT32, PART>(a, sc, NSRC, tailStart + (uint64_t)(th - h));
-  }
+template <class W, int NSRC, bool OUT32, bool PART>
+__global__ __launch_bounds__(kShiftLdsWaves * 64) void kWideShiftedLdsStats(KArgs a, WideSlot* slots) {
+  constexpr bool STATS = true;
+#include "nbx_wide_shifted.inc"
 }
 
 // ---------------------------------------------------------------------------
@@ -431,9 +381,10 @@ __global__ __launch_bounds__(kShiftLdsWaves * 64) void kWideShiftedLds(KArgs a) 
 
 // One head or tail element: wideElt's arithmetic, the source count a
 // template argument (as batchElt).
-template <class W, int NSRC, bool OUT32>
+template <class W, int NSRC, bool OUT32, bool STATS = false>
 __device__ __forceinline__ void wideBatchElt(const typename W::Elt* const (&src)[NSRC], void* const (&dst)[kMaxKDsts],
-                                             int nDsts, uint32_t preMask, float sc, uint64_t i) {
+                                             int nDsts, uint32_t preMask, float sc, uint64_t i,
+                                             WideLaneStats* ls = nullptr) {
   using E = typename W::Elt;
   float acc = W::wide(src[0][i]);
   if (preMask & 1u) acc = acc * sc;
@@ -443,6 +394,7 @@ __device__ __forceinline__ void wideBatchElt(const typename W::Elt* const (&src)
     if ((preMask >> s) & 1u) v = v * sc;
     acc = acc + v;
   }
+  if constexpr (STATS) ls->add(acc);
 #pragma unroll
   for (int d = 0; d < kMaxKDsts; d++) {
     if (d < nDsts) {
@@ -454,78 +406,15 @@ __device__ __forceinline__ void wideBatchElt(const typename W::Elt* const (&src)
 
 template <class W, int NSRC, bool OUT32>
 __global__ __launch_bounds__(kBlock) void kWideBatchList(BatchListArgs a) {
-  using E = typename W::Elt;
-  constexpr int EPP = W::kEPP, Q = EPP / 4;
-  const float sc = loadWideArg(a.argPtr, a.arg);
-  const uint32_t preMask = a.preMask;
-  const bool pre = preMask != 0;   // uniform per launch: the fold is never chosen per element
-  float mul[NSRC];
-#pragma unroll
-  for (int s = 0; s < NSRC; s++) mul[s] = ((preMask >> s) & 1u) ? sc : 1.0f;
-  const uint64_t T = a.totalTiles, C = a.chunk, step = (uint64_t)gridDim.x * C;
-  const int nRecs = a.nRecs, lane = (int)(threadIdx.x & 63u);
-  int k = -1;
-  uint64_t tBegin = 0, tEnd = 0, nElts = 0, n = 0;
-  int nDsts = 1, head = 0;
-  const E* sb[NSRC];
-  void* db[kMaxKDsts];
-  const u32x4* src[NSRC];
-  u32x4* dst[kMaxKDsts];
-  for (uint64_t c0 = (uint64_t)blockIdx.x * C; c0 < T; c0 += step) {
-    const uint64_t c1 = c0 + C < T ? c0 + C : T;
-    for (uint64_t tile = c0; tile < c1; tile++) {
-      if (tile >= tEnd) {   // next bucket holding this tile (uniform per wave)
-        for (int base = k + 1;; base += 64) {
-          const int idx = base + lane;
-          const uint64_t e = idx < nRecs ? (uint64_t)a.tileEnd[idx] : ~0ull;
-          const uint64_t m = __ballot(e > tile);
-          if (m != 0) {
-            k = __builtin_amdgcn_readfirstlane(base + (int)__builtin_ctzll(m));
-            break;
-          }
-        }
-        const uint64_t* r = a.recs + (uint64_t)k * a.recWords;
-        tBegin = r[0];
-        tEnd = r[1];
-        const uint64_t meta = r[2];
-        nDsts = (int)(meta >> 60);
-        nElts = meta & kBatchCountMask;
-        head = (int)((meta >> 56) & 15u);
-        n = (nElts - (uint64_t)head) / EPP;
-#pragma unroll
-        for (int s = 0; s < NSRC; s++) {
-          sb[s] = (const E*)r[3 + s];
-          src[s] = (const u32x4*)(sb[s] + head);
-        }
-#pragma unroll
-        for (int d = 0; d < kMaxKDsts; d++) {
-          db[d] = (void*)r[3 + NSRC + (d < nDsts ? d : 0)];
-          dst[d] = (u32x4*)((char*)db[d] + (uint64_t)head * (OUT32 ? sizeof(float) : sizeof(E)));
-        }
-      }
-      const uint64_t p = (tile - tBegin) * kBatchTilePacks + threadIdx.x;
-      if (p < n) {
-        u32x4 part[1][Q];   // no partial-first form: unused
-        u32x4 v[NSRC][1];
-#pragma unroll
-        for (int s = 0; s < NSRC; s++) v[s][0] = ldPack(src[s] + p);
-        // every load issued before the fold starts, as in kWidePacks (without
-        // this the widening of the first sources is scheduled between the
-        // loads, and a flat load's wait is a wait for all of them)
-        __builtin_amdgcn_sched_barrier(0);
-        if (pre) wideFoldStore<W, NSRC, 1, OUT32, false, true>(part, v, mul, dst, nDsts, p);
-        else wideFoldStore<W, NSRC, 1, OUT32, false, false>(part, v, mul, dst, nDsts, p);
-      }
-      if (tile == tEnd - 1) {   // the bucket's last tile: its head and tail elements
-        const uint64_t tailStart = (uint64_t)head + n * EPP;
-        const int tail = (int)(nElts - tailStart);
-        const int th = (int)threadIdx.x;
-        if (th < head) wideBatchElt<W, NSRC, OUT32>(sb, db, nDsts, preMask, sc, (uint64_t)th);
-        else if (th < head + tail)
-          wideBatchElt<W, NSRC, OUT32>(sb, db, nDsts, preMask, sc, tailStart + (uint64_t)(th - head));
-      }
-    }
-  }
+  constexpr bool STATS = false;
+  WideSlot* const slots = nullptr;
+#include "nbx_wide_batch.inc"
+}
+
+template <class W, int NSRC, bool OUT32>
+__global__ __launch_bounds__(kBlock) void kWideBatchListStats(BatchListArgs a, WideSlot* slots) {
+  constexpr bool STATS = true;
+#include "nbx_wide_batch.inc"
 }
 
 // ---------------------------------------------------------------------------
@@ -584,6 +473,58 @@ WideSet makeWideSet(int blocksPerCU) {
   ws.elts[0][1] = (const void*)&kWideElts<W, false, true>;
   ws.elts[1][0] = (const void*)&kWideElts<W, true, false>;
   ws.elts[1][1] = (const void*)&kWideElts<W, true, true>;
+  ws.eltBytes = (int)sizeof(typename W::Elt);
+  ws.blocksPerCU = blocksPerCU;
+  ws.valid = 1;
+  return ws;
+}
+
+// The STATS forms of one source type, in a WideSet of the statistics' own
+// table (WideStatsTable): the same indices, every entry a k...Stats kernel.
+// Every (output kind, partial-first, source count) can be a call's last pass,
+// so all of them exist.
+template <class W, bool OUT32, int... I, int... J>
+void fillWideStats(WideSet& ws, std::integer_sequence<int, I...>, std::integer_sequence<int, J...>) {
+  const void* first[] = {(const void*)&kWidePacksStats<W, I + 1, wideUnroll(I + 1), OUT32, false>...};
+  const void* later[] = {nullptr, (const void*)&kWidePacksStats<W, J + 2, wideUnroll(J + 2), OUT32, true>...};
+  const void* list[] = {(const void*)&kWideBatchListStats<W, I + 1, OUT32>...};
+  for (int i = 0; i < kMaxKSrcs; i++) {
+    ws.packs[OUT32 ? 1 : 0][0][i] = first[i];
+    ws.packs[OUT32 ? 1 : 0][1][i] = later[i];
+    ws.batchList[OUT32 ? 1 : 0][i] = list[i];
+  }
+  ws.elts[OUT32 ? 1 : 0][0] = (const void*)&kWideEltsStats<W, OUT32, false>;
+  ws.elts[OUT32 ? 1 : 0][1] = (const void*)&kWideEltsStats<W, OUT32, true>;
+}
+
+template <class W, bool OUT32, int... I, int... J>
+void fillWideShiftedStats(WideSet& ws, std::integer_sequence<int, I...>, std::integer_sequence<int, J...>) {
+  const void* first[] = {(const void*)&kWideShiftedLdsStats<W, I + 1, OUT32, false>...};
+  const void* later[] = {nullptr, (const void*)&kWideShiftedLdsStats<W, J + 2, OUT32, true>...};
+  for (int i = 0; i < kMaxKSrcs; i++) {
+    ws.shiftedLds[OUT32 ? 1 : 0][0][i] = first[i];
+    ws.shiftedLds[OUT32 ? 1 : 0][1][i] = later[i];
+  }
+}
+
+template <class Ty>
+void addWideShiftedStats(WideSet& ws) {
+  using W = WideTy<Ty>;
+  constexpr std::make_integer_sequence<int, kMaxKSrcs> all{};
+  constexpr std::make_integer_sequence<int, kMaxKSrcs - 1> fromTwo{};
+  fillWideShiftedStats<W, false>(ws, all, fromTwo);
+  fillWideShiftedStats<W, true>(ws, all, fromTwo);
+}
+
+// blocksPerCU: the plain set's (the grid does not enter the statistics).
+template <class Ty>
+WideSet makeWideStatsSet(int blocksPerCU) {
+  using W = WideTy<Ty>;
+  WideSet ws{};
+  constexpr std::make_integer_sequence<int, kMaxKSrcs> all{};
+  constexpr std::make_integer_sequence<int, kMaxKSrcs - 1> fromTwo{};
+  fillWideStats<W, false>(ws, all, fromTwo);
+  fillWideStats<W, true>(ws, all, fromTwo);
   ws.eltBytes = (int)sizeof(typename W::Elt);
   ws.blocksPerCU = blocksPerCU;
   ws.valid = 1;
