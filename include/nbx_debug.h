@@ -275,11 +275,21 @@ int nbxDebugReleaseStream(int hold);
  * in nbxDebugBatchListSlots(dev, 3) as for the per-step batch —, a capture
  * that cannot take a slot, batch mode 0). Batch modes 1 and 2 both mean work
  * lists here: there is no kernel-argument form.
+ * Passes of nbxReduceMultiWideMx — family: 17 block kernel (kMxBlocks),
+ * 18 any alignment (kMxGeneric). nSrcs as for the wide families; unroll: the
+ * 16-element groups per lane and tile (17), 1 (18). flags: bit 1 fp32 output
+ * (an MX-source call's, or an earlier pass's partial), bit 2 the first source
+ * is the fp32 partial, bit 4 the sources carry block scales. The earlier
+ * passes of a plain-source call of more than 8 sources are nbxReduceMultiWide's
+ * (families 6 / 7 / 16).
  * Plain host stores; the log keeps the newest 64 passes.
  * nbxDebugLaunchLog returns the number of passes since the last
  * nbxDebugLaunchLogReset() and copies the newest min(maxRecords, 64, that
  * number) of them, oldest first, four int32 each, to `out`. */
 int nbxDebugLaunchLog(int32_t* out, int maxRecords);
+/* Elements in one tile of nbxReduceMultiWideMx's block kernel for nSrcs (1..8)
+ * sources of srcType; 0 for any other argument. */
+int nbxDebugMxTileElts(ncclDataType_t srcType, int nSrcs);
 void nbxDebugLaunchLogReset(void);
 
 #ifdef __cplusplus

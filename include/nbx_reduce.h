@@ -273,6 +273,61 @@ ncclResult_t nbxReduceMultiWideBatchStats(const nbxReduceTask* tasks, int nTasks
                                           nbxDevRedOpFull op, int nPreOpSrcs,
                                           nbxWideStats* stats, ncclStream_t stream);
 
+/* MXFP8 block-scaled form of nbxReduceMultiWide (OCP microscaling, MX v1.0):
+ * 32-element blocks of fp8 codes with one E8M0 power-of-two scale byte each,
+ * as a destination, as the sources, or both. The fold is nbxReduceMultiWide's,
+ * bit for bit: every source widened exactly, one unfused fp32 multiply or add
+ * per step in source order, denormals kept, more than 8 sources in passes
+ * through an fp32 partial that is never narrowed.
+ * Blocks: block b is elements [32 b, 32 b + 32) of the bucket, counted from
+ * element 0 whatever the pointers' alignment; the last block holds count % 32
+ * elements when that is not 0. A scale array has ceil(count / 32) bytes.
+ * MX sources (srcScales != NULL, every entry non-NULL, srcType ncclFloat8e4m3
+ * or ncclFloat8e5m2): element i of source k is f32(code) * X, one fp32
+ * multiply, X = 2^(e - 127) for the scale byte e of its block (e = 0: the fp32
+ * denormal 2^-127; e = 0xFF: a NaN); the PreMulSum multiply (k < nPreOpSrcs)
+ * comes after it. srcScales == NULL: plain f16 / bf16 / fp8 sources.
+ * MX output (dstType ncclFloat8e4m3 or ncclFloat8e5m2, dstScales and every
+ * dstScales[d] non-NULL; dstType need not be srcType): with emax = 8 (e4m3) or
+ * 15 (e5m2) and m = max |a_i| over the block's final accumulators under
+ * nbxWideStats' amax rule (NaN if any a_i is NaN, else +inf if any is +-inf),
+ *   m finite:  the scale byte is S = max(be - emax, 0), be the biased exponent
+ *              field of m as fp32 (0 for zero and denormals) — MX v1.0's
+ *              floor(log2 m) - emax, biased by 127 and clamped at -127 — and
+ *              element i is narrow(a_i * R), R = 2^(127 - S) as fp32: one fp32
+ *              multiply, then the type's RNE-behind-SATFINITE narrowing (e4m3:
+ *              scaled values in (464, 512) store 448). An all-zero block has
+ *              scale byte 0 and keeps its signed zeros.
+ *   otherwise: the scale byte is 0xFF (MX's NaN block) and element i is
+ *              narrow(a_i), unscaled: the non-finite positions stay visible.
+ * The multiply by R is exact except where the product falls below 2^-126, and
+ * such a value narrows to +-0 whether it was rounded or flushed: the stored
+ * bits are a function of the arguments alone, whichever kernel runs.
+ * fp32 output (dstType ncclFloat32, dstScales NULL): the accumulators as they
+ * are; only with MX sources (plain sources into fp32 is nbxReduceMultiWide:
+ * here ncclInvalidArgument).
+ * op: nbxDevSum or nbxDevPreMulSum with the fp32 scalar of nbxReduceMultiWide
+ * (by value or by device pointer); everything else ncclInvalidArgument. Every
+ * check of nbxReduceMultiWide applies, and every check is made before any
+ * device call; count == 0 is a no-op after the type and op checks. Element
+ * pointers are aligned to their element size, scale pointers to nothing.
+ * Overlap: a destination's element buffer may be one of the sources only when
+ * srcType == dstType, and if that source carries scales the destination's
+ * scale array must be that source's; any other overlap between a destination
+ * (elements or scales) and a source (elements or scales), or between the two
+ * arrays of one destination, is ncclInvalidArgument.
+ * Every element pointer 16-byte aligned and every destination scale pointer
+ * 4-byte aligned runs the block kernel (a lane pair per block, the scale bytes
+ * stored as dwords); any other layout one element per lane. Same bits.
+ * Stream-ordered, asynchronous and graph-capturable.
+ * Not provided: MXFP6 / MXFP4 elements, block sizes other than 32, a batched
+ * form, a statistics form, a form inside the collectives, a host-staged form,
+ * a realigning LDS-DMA form. */
+ncclResult_t nbxReduceMultiWideMx(void* const* dsts, void* const* dstScales, int nDsts,
+                                  const void* const* srcs, const void* const* srcScales, int nSrcs,
+                                  size_t count, ncclDataType_t srcType, ncclDataType_t dstType,
+                                  nbxDevRedOpFull op, int nPreOpSrcs, ncclStream_t stream);
+
 /* Host-staged form of nbxReduceMulti: sources and destinations in HOST memory
  * (pinned for full speed; pageable works), the path NCCL's NET/SHM transports
  * stage through (host-pinned proxy FIFOs net.cc:735/883, /dev/shm buffers

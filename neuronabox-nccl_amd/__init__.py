@@ -179,6 +179,9 @@ _SIGS = {
                                 ctypes.c_void_p, ctypes.c_void_p],
     "nbxReduceMultiWideBatchStats": [ctypes.POINTER(ReduceTask), ctypes.c_int, ctypes.c_int, ctypes.c_int,
                                      DevRedOpFull, ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p],
+    "nbxReduceMultiWideMx": [ctypes.POINTER(ctypes.c_void_p), ctypes.POINTER(ctypes.c_void_p), ctypes.c_int,
+                             ctypes.POINTER(ctypes.c_void_p), ctypes.POINTER(ctypes.c_void_p), ctypes.c_int,
+                             ctypes.c_size_t, ctypes.c_int, ctypes.c_int, DevRedOpFull, ctypes.c_int, ctypes.c_void_p],
     "nbxRedOpCreateWide": [ctypes.POINTER(ctypes.c_int), ctypes.c_int, ctypes.c_int, ctypes.c_void_p],
     "nbxSetLaunchConfig": [ctypes.c_int, ctypes.c_int],
     "nbxGetLaunchConfig": [ctypes.POINTER(ctypes.c_int), ctypes.POINTER(ctypes.c_int)],
@@ -240,6 +243,8 @@ def load_library(path: Optional[str] = None) -> ctypes.CDLL:
                                        ctypes.c_int, ctypes.c_size_t, ctypes.c_int, ctypes.c_int,
                                        ctypes.POINTER(ctypes.c_size_t)]
     lib.nbxDebugWideLayout.restype = ctypes.c_int
+    lib.nbxDebugMxTileElts.argtypes = [ctypes.c_int, ctypes.c_int]
+    lib.nbxDebugMxTileElts.restype = ctypes.c_int
     # test hook of the Simple transport: counters and flag words of a communicator at rest
     lib.nbxDebugSimpleState.argtypes = [ctypes.c_void_p, ctypes.POINTER(ctypes.c_uint64),
                                         ctypes.POINTER(ctypes.c_uint64), ctypes.c_size_t, ctypes.POINTER(ctypes.c_int)]
@@ -374,10 +379,13 @@ class LaunchFamily(enum.IntEnum):        # include/nbx_debug.h nbxDebugLaunchLog
     BatchList = 14
     WideBatchList = 15    # nbxReduceMultiWideBatch launches: flags bit 1 = fp32 output, bits 8.. = buckets
     WideRealignLds = 16   # nbxReduceMultiWide's realigning kernel (kWideShiftedLds)
+    MxBlocks = 17         # nbxReduceMultiWideMx: a lane pair per 32-element block (kMxBlocks)
+    MxGeneric = 18        # ... any alignment, one element per lane (kMxGeneric)
 
 
 LAUNCH_DYNAMIC, LAUNCH_OUT32, LAUNCH_PART_FIRST = 1, 2, 4
 LAUNCH_STATS = 8   # wide families 6 / 7 / 15 / 16: the STATS form ran (nbxReduceMultiWideStats)
+LAUNCH_MX_SCALED = 16   # MX families 17 / 18: the sources carry block scales
 WIDE_STATS_L = 32  # fp32 roundings into one fp64 partial: sumSq is exact within L * 2^-24 (include/nbx_reduce.h)
 LAUNCH_CHECKED, LAUNCH_SEGS_SHIFT = 1, 8   # collective families: checking instantiation, group segments (batch: buckets)
 LAUNCH_LOG_CAP = 64
@@ -461,6 +469,39 @@ def reduce_multi_wide_stats(dsts: Sequence[int], srcs: Sequence[int], count: int
     accumulators, before any narrowing) to the 16 device bytes at `stats`."""
     _check(reduce_multi_wide_stats_raw(dsts, srcs, count, src_type, dst_type, op, stats, n_pre_op_srcs, stream),
            "nbxReduceMultiWideStats")
+
+
+MX_BLOCK = 32   # elements per MXFP8 block: one E8M0 scale byte each (include/nbx_reduce.h)
+
+
+def _ptr_array(ptrs: Optional[Sequence[int]]):
+    if ptrs is None:
+        return None
+    return (ctypes.c_void_p * max(1, len(ptrs)))(*[ctypes.c_void_p(int(x)) for x in ptrs])
+
+
+def reduce_multi_wide_mx_raw(dsts: Sequence[int], dst_scales: Optional[Sequence[int]], srcs: Sequence[int],
+                             src_scales: Optional[Sequence[int]], count: int, src_type: int, dst_type: int,
+                             op: DevRedOpFull, n_pre_op_srcs: int = 0, stream: int = 0) -> int:
+    """Call nbxReduceMultiWideMx (a scale list of None is the NULL array); returns the code."""
+    return load_library().nbxReduceMultiWideMx(_ptr_array(dsts), _ptr_array(dst_scales), len(dsts), _ptr_array(srcs),
+                                               _ptr_array(src_scales), len(srcs), int(count), int(src_type),
+                                               int(dst_type), op, int(n_pre_op_srcs), ctypes.c_void_p(int(stream)))
+
+
+def reduce_multi_wide_mx(dsts: Sequence[int], dst_scales: Optional[Sequence[int]], srcs: Sequence[int],
+                         src_scales: Optional[Sequence[int]], count: int, src_type: int, dst_type: int,
+                         op: DevRedOpFull, n_pre_op_srcs: int = 0, stream: int = 0) -> None:
+    """reduce_multi_wide with MXFP8 on either side: `dst_scales` (one byte per 32 elements beside each
+    fp8 destination) for a block-scaled output, `src_scales` for block-scaled fp8 sources; with
+    `src_scales` the output may also be fp32 (`dst_scales` None)."""
+    _check(reduce_multi_wide_mx_raw(dsts, dst_scales, srcs, src_scales, count, src_type, dst_type, op, n_pre_op_srcs,
+                                    stream), "nbxReduceMultiWideMx")
+
+
+def mx_tile_elts(src_type: int, n_srcs: int) -> int:
+    """Elements per tile of nbxReduceMultiWideMx's block kernel (nbxDebugMxTileElts)."""
+    return int(load_library().nbxDebugMxTileElts(int(src_type), int(n_srcs)))
 
 
 WIDE_LAYOUT_ELEMENTS, WIDE_LAYOUT_PACKS, WIDE_LAYOUT_REALIGN = 0, 1, 2   # nbxDebugWideLayout

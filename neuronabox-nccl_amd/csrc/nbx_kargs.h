@@ -147,6 +147,36 @@ struct WideSet {
   int valid;
 };
 
+// MXFP8 block-scaled form of the fp32-accumulating sums (nbx_mx.h,
+// nbxReduceMultiWideMx): 32-element blocks, one E8M0 scale byte each. A lane of
+// the block kernel holds one 16-element group (half a block: one dwordx4 of
+// fp8 codes), so a tile is mxUnroll x kBlock groups. The packs per lane and
+// source follow wideUnroll: an fp8 group is one pack, a 16-bit group two, so
+// the 16-bit tile holds half the groups (and never less than one).
+constexpr int kMxBlockElts = 32;
+constexpr int kMxGroupElts = 16;
+constexpr int mxUnroll(int nSrcs, int eltBytes) {
+  return eltBytes == 1 ? wideUnroll(nSrcs) : (wideUnroll(nSrcs) >= 2 ? wideUnroll(nSrcs) / 2 : 1);
+}
+
+// The scale arrays travel as a second kernel argument, so KArgs is what it was.
+struct MxArgs {
+  const uint8_t* srcScale[kMaxKSrcs];   // scaled sources only; slot 0 unused behind a partial
+  uint8_t* dstScale[kMaxKDsts];         // fp8 outputs only
+};
+
+// Launch table of one source kind: f16, bf16, e4m3, e5m2 plain, e4m3 / e5m2
+// with scales. [output: 0 e4m3, 1 e5m2, 2 fp32 (scaled kinds only)][source 0
+// is an fp32 partial][nSrcs-1]; the generic kernel takes nSrcs at run time.
+constexpr int kMxKinds = 6, kMxOuts = 3;
+struct MxSet {
+  const void* blocks[kMxOuts][2][kMaxKSrcs];
+  const void* generic[kMxOuts][2];
+  int eltBytes;
+  int scaled;
+  int valid;
+};
+
 // Bucket statistics of the fp32-accumulating sums (nbxReduceMultiWideStats,
 // nbx_wide.h "Bucket statistics"). The STATS kernels take the slot array as a
 // second kernel argument, so KArgs and BatchListArgs are what they were.

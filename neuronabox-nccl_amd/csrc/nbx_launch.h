@@ -22,6 +22,7 @@ namespace nbx {
 const KernelTable& table();       // nbx_reduce.cc
 const WideTable& wideTable();     // nbx_reduce_wide.cc
 const WideStatsTable& wideStatsTable();   // the STATS forms, same indices (nbx_reduce_wide.cc)
+const MxTable& mxTable();         // the MXFP8 block-scaled sums, by source kind (nbx_reduce_mx.cc)
 int typeSize(int dt);             // bytes of an ncclDataType_t, -1 unknown (nbx_reduce.cc)
 
 // ---- launch policy, device and stream helpers (nbx_policy.cc) ----
@@ -86,10 +87,12 @@ enum LaunchFamily {
   kFamWideElts = 7,
   kFamBatch = 13, kFamBatchList = 14,   // batched buckets: flags bits kLaunchSegsShift.. = buckets of the launch
   kFamWideBatchList = 15,               // the same for nbxReduceMultiWideBatch (bit 1: fp32 output)
-  kFamWideShiftedLds = 16               // wide realigning LDS-DMA (kWideShiftedLds)
+  kFamWideShiftedLds = 16,              // wide realigning LDS-DMA (kWideShiftedLds)
+  kFamMxBlocks = 17, kFamMxGeneric = 18 // nbxReduceMultiWideMx: block kernel (kMxBlocks), any alignment (kMxGeneric)
 };
 // kLaunchStats: the STATS form of a wide family (6 / 7 / 15 / 16) ran
-enum LaunchFlag { kLaunchDynamic = 1, kLaunchOut32 = 2, kLaunchPartFirst = 4, kLaunchStats = 8 };
+// kLaunchMxScaled: the sources of an MX family (17 / 18) carry block scales
+enum LaunchFlag { kLaunchDynamic = 1, kLaunchOut32 = 2, kLaunchPartFirst = 4, kLaunchStats = 8, kLaunchMxScaled = 16 };
 void logLaunch(int family, int nSrcs, int unroll, int flags);
 
 // Argument checks the batched entry points share with the single ones.

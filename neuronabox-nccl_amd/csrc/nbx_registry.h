@@ -49,4 +49,14 @@ WideStatsKernels wideStatsKernels();
 typedef WideCollSet WideCollTable[kNumTypes];
 void fillWideColl16(WideCollTable& t);
 void fillWideColl8(WideCollTable& t);
+
+// the MXFP8 block-scaled sums (nbxReduceMultiWideMx): one MxSet per source
+// kind, a unit per kind (inst_mx_*.hip)
+typedef MxSet MxTable[kMxKinds];
+void fillMxF16(MxTable& t);
+void fillMxBF16(MxTable& t);
+void fillMxE4M3(MxTable& t);
+void fillMxE5M2(MxTable& t);
+void fillMxE4M3Scaled(MxTable& t);
+void fillMxE5M2Scaled(MxTable& t);
 }  // namespace nbx
