@@ -281,7 +281,10 @@ int nbxDebugReleaseStream(int hold);
  * (an MX-source call's, or an earlier pass's partial), bit 2 the first source
  * is the fp32 partial, bit 4 the sources carry block scales. The earlier
  * passes of a plain-source call of more than 8 sources are nbxReduceMultiWide's
- * (families 6 / 7 / 16).
+ * (families 6 / 7 / 16). Its MXFP4 forms (NBX_FLOAT4_E2M1) — family: 19 quad
+ * layout (kMx4Blocks), 20 any alignment (kMx4Generic); unroll: the 8-element
+ * groups per lane and tile (19), 1 (20); flags as for 17 / 18, bit 4 set for
+ * MXFP4 sources.
  * Plain host stores; the log keeps the newest 64 passes.
  * nbxDebugLaunchLog returns the number of passes since the last
  * nbxDebugLaunchLogReset() and copies the newest min(maxRecords, 64, that
@@ -290,6 +293,9 @@ int nbxDebugLaunchLog(int32_t* out, int maxRecords);
 /* Elements in one tile of nbxReduceMultiWideMx's block kernel for nSrcs (1..8)
  * sources of srcType; 0 for any other argument. */
 int nbxDebugMxTileElts(ncclDataType_t srcType, int nSrcs);
+/* The same for the MXFP4 block kernel: srcType ncclFloat16, ncclBfloat16 or
+ * NBX_FLOAT4_E2M1. */
+int nbxDebugMx4TileElts(ncclDataType_t srcType, int nSrcs);
 void nbxDebugLaunchLogReset(void);
 
 #ifdef __cplusplus

@@ -320,9 +320,38 @@ ncclResult_t nbxReduceMultiWideBatchStats(const nbxReduceTask* tasks, int nTasks
  * 4-byte aligned runs the block kernel (a lane pair per block, the scale bytes
  * stored as dwords); any other layout one element per lane. Same bits.
  * Stream-ordered, asynchronous and graph-capturable.
- * Not provided: MXFP6 / MXFP4 elements, block sizes other than 32, a batched
- * form, a statistics form, a form inside the collectives, a host-staged form,
- * a realigning LDS-DMA form. */
+ *
+ * MXFP4 (OCP E2M1) elements: NBX_FLOAT4_E2M1 as srcType, dstType or both, a tag
+ * only this function accepts. An FP4 buffer holds ceil(count / 2) bytes:
+ * element 2 j is the low nibble of byte j, element 2 j + 1 the high nibble;
+ * element 0 is always a low nibble, so the pointer is byte-aligned. For an odd
+ * count a destination's last high nibble is stored as 0 and a source's is
+ * ignored. A code is a sign (bit 3) over the magnitudes 0, 0.5, 1, 1.5, 2, 3,
+ * 4, 6 (codes 0 - 7). Blocks and scale arrays are as above.
+ *   ncclFloat16 / ncclBfloat16 sources (srcScales NULL) into MXFP4 (dstScales
+ *     given);
+ *   MXFP4 sources (srcScales and every entry non-NULL) into MXFP4, or into
+ *     fp32 (dstScales NULL).
+ * An MXFP4 source element is f32(code) * X with the X above (exact for every
+ * code and finite scale), the PreMulSum multiply after it. The fold is the
+ * same. MXFP4 output follows the MX output rule with emax = 2: for finite m,
+ * S = max(be - 2, 0), R = 2^(127 - S), and element i is narrow4(a_i * R): one
+ * fp32 multiply, then round-to-nearest-even onto the eight magnitudes (the
+ * ties 0.25, 1.25, 2.5 and 5 round down, 0.75, 1.75 and 3.5 up), everything
+ * above 6 stored as +-6 (the scaled maximum lies in [4, 8), so (6, 8)
+ * saturates, as e4m3's (464, 512)), the sign kept: -0 is 0x8 and magnitudes
+ * below 0.25 give +-0. The type has no NaN or inf code: for a non-finite m the
+ * scale byte is 0xFF and EVERY code of the block is 0, and a reader — this
+ * function included — takes every element of a 0xFF block as NaN.
+ * Overlap as above with ceil(count / 2) as an FP4 array's size; in place only
+ * MXFP4 into MXFP4, on the source's own scale array. The block kernel (a lane
+ * quad per block) needs the same alignments; any other layout runs one FP4
+ * byte per lane. Same bits.
+ * Not provided (ncclInvalidArgument): MXFP6; fp8 sources, plain or MX, into
+ * MXFP4; MXFP4 sources into MXFP8; MXFP4 sources without scales; block sizes
+ * other than 32; a batched form, a statistics form, a form inside the
+ * collectives, a host-staged form, a realigning LDS-DMA form. */
+#define NBX_FLOAT4_E2M1 ((ncclDataType_t)32)
 ncclResult_t nbxReduceMultiWideMx(void* const* dsts, void* const* dstScales, int nDsts,
                                   const void* const* srcs, const void* const* srcScales, int nSrcs,
                                   size_t count, ncclDataType_t srcType, ncclDataType_t dstType,

@@ -245,6 +245,8 @@ def load_library(path: Optional[str] = None) -> ctypes.CDLL:
     lib.nbxDebugWideLayout.restype = ctypes.c_int
     lib.nbxDebugMxTileElts.argtypes = [ctypes.c_int, ctypes.c_int]
     lib.nbxDebugMxTileElts.restype = ctypes.c_int
+    lib.nbxDebugMx4TileElts.argtypes = [ctypes.c_int, ctypes.c_int]
+    lib.nbxDebugMx4TileElts.restype = ctypes.c_int
     # test hook of the Simple transport: counters and flag words of a communicator at rest
     lib.nbxDebugSimpleState.argtypes = [ctypes.c_void_p, ctypes.POINTER(ctypes.c_uint64),
                                         ctypes.POINTER(ctypes.c_uint64), ctypes.c_size_t, ctypes.POINTER(ctypes.c_int)]
@@ -381,11 +383,13 @@ class LaunchFamily(enum.IntEnum):        # include/nbx_debug.h nbxDebugLaunchLog
     WideRealignLds = 16   # nbxReduceMultiWide's realigning kernel (kWideShiftedLds)
     MxBlocks = 17         # nbxReduceMultiWideMx: a lane pair per 32-element block (kMxBlocks)
     MxGeneric = 18        # ... any alignment, one element per lane (kMxGeneric)
+    Mx4Blocks = 19        # its MXFP4 forms: a lane quad per block (kMx4Blocks)
+    Mx4Generic = 20       # ... any alignment, one FP4 byte per lane (kMx4Generic)
 
 
 LAUNCH_DYNAMIC, LAUNCH_OUT32, LAUNCH_PART_FIRST = 1, 2, 4
 LAUNCH_STATS = 8   # wide families 6 / 7 / 15 / 16: the STATS form ran (nbxReduceMultiWideStats)
-LAUNCH_MX_SCALED = 16   # MX families 17 / 18: the sources carry block scales
+LAUNCH_MX_SCALED = 16   # MX families 17 - 20: the sources carry block scales
 WIDE_STATS_L = 32  # fp32 roundings into one fp64 partial: sumSq is exact within L * 2^-24 (include/nbx_reduce.h)
 LAUNCH_CHECKED, LAUNCH_SEGS_SHIFT = 1, 8   # collective families: checking instantiation, group segments (batch: buckets)
 LAUNCH_LOG_CAP = 64
@@ -471,7 +475,8 @@ def reduce_multi_wide_stats(dsts: Sequence[int], srcs: Sequence[int], count: int
            "nbxReduceMultiWideStats")
 
 
-MX_BLOCK = 32   # elements per MXFP8 block: one E8M0 scale byte each (include/nbx_reduce.h)
+MX_BLOCK = 32   # elements per MX block: one E8M0 scale byte each (include/nbx_reduce.h)
+FLOAT4_E2M1 = 32   # NBX_FLOAT4_E2M1: MXFP4 elements, two codes per byte; reduce_multi_wide_mx alone takes it
 
 
 def _ptr_array(ptrs: Optional[Sequence[int]]):
@@ -494,7 +499,8 @@ def reduce_multi_wide_mx(dsts: Sequence[int], dst_scales: Optional[Sequence[int]
                          op: DevRedOpFull, n_pre_op_srcs: int = 0, stream: int = 0) -> None:
     """reduce_multi_wide with MXFP8 on either side: `dst_scales` (one byte per 32 elements beside each
     fp8 destination) for a block-scaled output, `src_scales` for block-scaled fp8 sources; with
-    `src_scales` the output may also be fp32 (`dst_scales` None)."""
+    `src_scales` the output may also be fp32 (`dst_scales` None). FLOAT4_E2M1 as either type: MXFP4,
+    two codes per byte (f16 / bf16 or MXFP4 sources into MXFP4; MXFP4 sources into fp32)."""
     _check(reduce_multi_wide_mx_raw(dsts, dst_scales, srcs, src_scales, count, src_type, dst_type, op, n_pre_op_srcs,
                                     stream), "nbxReduceMultiWideMx")
 
@@ -502,6 +508,11 @@ def reduce_multi_wide_mx(dsts: Sequence[int], dst_scales: Optional[Sequence[int]
 def mx_tile_elts(src_type: int, n_srcs: int) -> int:
     """Elements per tile of nbxReduceMultiWideMx's block kernel (nbxDebugMxTileElts)."""
     return int(load_library().nbxDebugMxTileElts(int(src_type), int(n_srcs)))
+
+
+def mx4_tile_elts(src_type: int, n_srcs: int) -> int:
+    """Elements per tile of the MXFP4 block kernel (nbxDebugMx4TileElts)."""
+    return int(load_library().nbxDebugMx4TileElts(int(src_type), int(n_srcs)))
 
 
 WIDE_LAYOUT_ELEMENTS, WIDE_LAYOUT_PACKS, WIDE_LAYOUT_REALIGN = 0, 1, 2   # nbxDebugWideLayout

@@ -177,6 +177,25 @@ struct MxSet {
   int valid;
 };
 
+// MXFP4 elements in the same call (nbx_mx4.h): two codes per byte, so a lane of
+// the block kernel holds one 8-element group (a quarter of a block: one dword
+// of codes, one dwordx4 of a 16-bit source) and a tile is mx4Unroll x kBlock
+// groups. An FP4 source brings 4 bytes per lane and step, so its tiles are deep;
+// a 16-bit source brings the wide kernels' 16.
+constexpr int kMx4GroupElts = 8;
+constexpr int kTypeFp4 = 32;   // NBX_FLOAT4_E2M1 (include/nbx_reduce.h): a tag outside ncclDataType_t's own values
+constexpr int mx4Unroll(int nSrcs, bool fp4) { return fp4 ? (nSrcs <= 4 ? 8 : 4) : (nSrcs >= 4 ? 4 : 2); }
+
+// Launch table of one source kind: f16, bf16 plain, MXFP4. [output: 0 MXFP4,
+// 1 fp32 (MXFP4 sources only)][source 0 is an fp32 partial][nSrcs-1].
+constexpr int kMx4Kinds = 3;
+struct Mx4Set {
+  const void* blocks[2][2][kMaxKSrcs];
+  const void* generic[2][2];
+  int fp4;
+  int valid;
+};
+
 // Bucket statistics of the fp32-accumulating sums (nbxReduceMultiWideStats,
 // nbx_wide.h "Bucket statistics"). The STATS kernels take the slot array as a
 // second kernel argument, so KArgs and BatchListArgs are what they were.

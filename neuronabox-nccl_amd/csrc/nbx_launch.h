@@ -23,6 +23,10 @@ const KernelTable& table();       // nbx_reduce.cc
 const WideTable& wideTable();     // nbx_reduce_wide.cc
 const WideStatsTable& wideStatsTable();   // the STATS forms, same indices (nbx_reduce_wide.cc)
 const MxTable& mxTable();         // the MXFP8 block-scaled sums, by source kind (nbx_reduce_mx.cc)
+// the MXFP4 forms of nbxReduceMultiWideMx: every call that names NBX_FLOAT4_E2M1 (nbx_reduce_mx4.cc)
+ncclResult_t reduceMultiWideMx4(void* const* dsts, void* const* dstScales, int nDsts, const void* const* srcs,
+                                const void* const* srcScales, int nSrcs, size_t count, ncclDataType_t srcType,
+                                ncclDataType_t dstType, nbxDevRedOpFull op, int nPreOpSrcs, ncclStream_t stream);
 int typeSize(int dt);             // bytes of an ncclDataType_t, -1 unknown (nbx_reduce.cc)
 
 // ---- launch policy, device and stream helpers (nbx_policy.cc) ----
@@ -88,10 +92,11 @@ enum LaunchFamily {
   kFamBatch = 13, kFamBatchList = 14,   // batched buckets: flags bits kLaunchSegsShift.. = buckets of the launch
   kFamWideBatchList = 15,               // the same for nbxReduceMultiWideBatch (bit 1: fp32 output)
   kFamWideShiftedLds = 16,              // wide realigning LDS-DMA (kWideShiftedLds)
-  kFamMxBlocks = 17, kFamMxGeneric = 18 // nbxReduceMultiWideMx: block kernel (kMxBlocks), any alignment (kMxGeneric)
+  kFamMxBlocks = 17, kFamMxGeneric = 18,  // nbxReduceMultiWideMx: block kernel (kMxBlocks), any alignment (kMxGeneric)
+  kFamMx4Blocks = 19, kFamMx4Generic = 20 // its MXFP4 forms: quad layout (kMx4Blocks), any alignment (kMx4Generic)
 };
 // kLaunchStats: the STATS form of a wide family (6 / 7 / 15 / 16) ran
-// kLaunchMxScaled: the sources of an MX family (17 / 18) carry block scales
+// kLaunchMxScaled: the sources of an MX family (17 - 20) carry block scales
 enum LaunchFlag { kLaunchDynamic = 1, kLaunchOut32 = 2, kLaunchPartFirst = 4, kLaunchStats = 8, kLaunchMxScaled = 16 };
 void logLaunch(int family, int nSrcs, int unroll, int flags);
 

@@ -100,6 +100,9 @@ NBX_EXPORT ncclResult_t nbxReduceMultiWideMx(void* const* dsts, void* const* dst
                                              const void* const* srcs, const void* const* srcScales, int nSrcs,
                                              size_t count, ncclDataType_t srcType, ncclDataType_t dstType,
                                              nbxDevRedOpFull op, int nPreOpSrcs, ncclStream_t stream) {
+  if ((int)srcType == kTypeFp4 || (int)dstType == kTypeFp4)   // MXFP4: nbx_reduce_mx4.cc
+    return reduceMultiWideMx4(dsts, dstScales, nDsts, srcs, srcScales, nSrcs, count, srcType, dstType, op, nPreOpSrcs,
+                              stream);
   // ---- checks: all of them before any device call ----
   if (!argArraysOk(dsts, nDsts, srcs, nSrcs)) return ncclInvalidArgument;
   ncclResult_t cr = checkWideOp(srcType, srcType, op);   // the four source types, Sum / PreMulSum, the scalar

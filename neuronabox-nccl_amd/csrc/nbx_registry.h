@@ -59,4 +59,11 @@ void fillMxE4M3(MxTable& t);
 void fillMxE5M2(MxTable& t);
 void fillMxE4M3Scaled(MxTable& t);
 void fillMxE5M2Scaled(MxTable& t);
+
+// its MXFP4 forms (NBX_FLOAT4_E2M1, nbx_mx4.h): one Mx4Set per source kind, a
+// unit per kind (inst_mx4_*.hip)
+typedef Mx4Set Mx4Table[kMx4Kinds];
+void fillMx4F16(Mx4Table& t);
+void fillMx4BF16(Mx4Table& t);
+void fillMx4Fp4(Mx4Table& t);
 }  // namespace nbx
