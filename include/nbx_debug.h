@@ -211,8 +211,8 @@ int nbxDebugHoldStream(ncclStream_t stream, int timeoutMs);
 int nbxDebugReleaseStream(int hold);
 
 /* Launch record (test hook): every kernel pass that nbxReduceMulti /
- * nbxReduceMultiWide / nbxReduceMultiBatch / nbxReduceMultiWideBatch launch
- * from the calling thread, and
+ * nbxReduceMultiWide / nbxReduceMultiBatch / nbxReduceMultiWideBatch /
+ * nbxReduceMultiWideMx / nbxReduceMultiWideMxBatch launch from the calling thread, and
  * every collective kernel a multi-rank communicator launches from it, appends
  * {family, nSrcs, unroll, flags} to a thread-local log, so a test can see
  * which kernel a call took.
@@ -285,6 +285,20 @@ int nbxDebugReleaseStream(int hold);
  * layout (kMx4Blocks), 20 any alignment (kMx4Generic); unroll: the 8-element
  * groups per lane and tile (19), 1 (20); flags as for 17 / 18, bit 4 set for
  * MXFP4 sources.
+ * Batched launches of nbxReduceMultiWideMxBatch (nbx_reduce_mx_batch.cc
+ * launchMxBatchList), one record per kernel launched, after the launch
+ * succeeded — family: 21 MX work-list batch (kMxBatchList). nSrcs: the
+ * launch's source count. unroll: 1. flags: bit 1 fp32 output, bit 4 the
+ * sources carry block scales, bits 8.. the buckets of that launch (buckets of
+ * count 0 are never counted). Buckets that do not go into a batch leave the
+ * records of nbxReduceMultiWideMx, families 17 and 18 (and 6 / 7 / 16 for the
+ * earlier passes of more than 8 plain sources). Order of one call's records
+ * as for nbxReduceMultiWideBatch: first, in bucket order, the buckets that run
+ * alone (another layout, > 8 sources, 4+ sources filling the GPU alone, every
+ * bucket under launch variant 2); then, per source count ascending, that
+ * count's work-list launches followed by one family-17 launch for each of its
+ * buckets that got no table slot (arena exhausted, a capture that cannot take
+ * a slot, batch mode 0).
  * Plain host stores; the log keeps the newest 64 passes.
  * nbxDebugLaunchLog returns the number of passes since the last
  * nbxDebugLaunchLogReset() and copies the newest min(maxRecords, 64, that
@@ -296,6 +310,9 @@ int nbxDebugMxTileElts(ncclDataType_t srcType, int nSrcs);
 /* The same for the MXFP4 block kernel: srcType ncclFloat16, ncclBfloat16 or
  * NBX_FLOAT4_E2M1. */
 int nbxDebugMx4TileElts(ncclDataType_t srcType, int nSrcs);
+/* Elements in one tile of nbxReduceMultiWideMxBatch's kernel (kMxBatchList):
+ * 4096 for every source type and count. */
+int nbxDebugMxBatchTileElts(void);
 void nbxDebugLaunchLogReset(void);
 
 #ifdef __cplusplus

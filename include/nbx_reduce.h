@@ -349,13 +349,58 @@ ncclResult_t nbxReduceMultiWideBatchStats(const nbxReduceTask* tasks, int nTasks
  * byte per lane. Same bits.
  * Not provided (ncclInvalidArgument): MXFP6; fp8 sources, plain or MX, into
  * MXFP4; MXFP4 sources into MXFP8; MXFP4 sources without scales; block sizes
- * other than 32; a batched form, a statistics form, a form inside the
+ * other than 32; a batched form of MXFP4 (MXFP8 has one:
+ * nbxReduceMultiWideMxBatch), a statistics form, a form inside the
  * collectives, a host-staged form, a realigning LDS-DMA form. */
 #define NBX_FLOAT4_E2M1 ((ncclDataType_t)32)
 ncclResult_t nbxReduceMultiWideMx(void* const* dsts, void* const* dstScales, int nDsts,
                                   const void* const* srcs, const void* const* srcScales, int nSrcs,
                                   size_t count, ncclDataType_t srcType, ncclDataType_t dstType,
                                   nbxDevRedOpFull op, int nPreOpSrcs, ncclStream_t stream);
+
+/* One bucket of nbxReduceMultiWideMxBatch: nbxReduceMultiWideMx's arrays and
+ * count. dstScales is NULL for an fp32 output, srcScales for plain sources. */
+typedef struct {
+  void* const* dsts;        void* const* dstScales;        int nDsts;
+  const void* const* srcs;  const void* const* srcScales;  int nSrcs;
+  size_t count;
+} nbxReduceMxTask;
+
+/* Batched form of nbxReduceMultiWideMx for MXFP8: behaves as if
+ * nbxReduceMultiWideMx(t.dsts, t.dstScales, t.nDsts, t.srcs, t.srcScales,
+ * t.nSrcs, t.count, srcType, dstType, op, nPreOpSrcs, stream) were called for
+ * every bucket t, in far fewer launches; the results are the same bits for
+ * every layout. Buckets in the block kernel's layout (every element pointer
+ * 16-byte aligned, every destination scale pointer 4-byte aligned) with at
+ * most 8 sources share work-list launches per source count, up to 384 buckets
+ * each (fewer for wide records: 219 for 8 scaled sources and 8 MX
+ * destinations), tiles of 4096 elements in one index space; every other
+ * bucket — any other layout, more than 8 sources, 4+ sources filling the GPU
+ * alone, no table slot left — is one nbxReduceMultiWideMx launch.
+ * Types: the six source kinds of nbxReduceMultiWideMx's MXFP8 form (f16, bf16,
+ * e4m3, e5m2 plain; e4m3, e5m2 with scales) into MX e4m3, MX e5m2 and, for
+ * scaled sources, fp32. NBX_FLOAT4_E2M1 on either side: ncclInvalidArgument.
+ * Scaled or plain is a property of the call: every task's srcScales is NULL or
+ * every task's is non-NULL, empty buckets included; a mixture is
+ * ncclInvalidArgument, and so is a task whose dstScales does not suit dstType.
+ * Checks: the type, op and scalar checks of nbxReduceMultiWideMx, made even
+ * for nTasks == 0 (then a no-op); nTasks < 0 or tasks == NULL with nTasks > 0:
+ * ncclInvalidArgument. Every bucket gets every check of the single call
+ * (counts of pointers, NULL entries, element alignment, the overlap rules, in
+ * place only with equal types on the source's own scale array) before
+ * anything is enqueued and before any device call; buckets of count 0 are
+ * skipped, the entries of their arrays unexamined, as in the single call.
+ * Buckets must be independent of each other, scale arrays included: no
+ * bucket's destination or destination scales may overlap anything another
+ * bucket reads or writes (the caller's contract, as for
+ * nbxReduceMultiWideBatch; not checked).
+ * Stream-ordered, asynchronous and graph-capturable: a table written during
+ * capture belongs to the graph until it is destroyed. Nothing ever waits for a
+ * table slot.
+ * Not provided: MXFP4 in the batch, statistics, a kernel-argument form. */
+ncclResult_t nbxReduceMultiWideMxBatch(const nbxReduceMxTask* tasks, int nTasks,
+                                       ncclDataType_t srcType, ncclDataType_t dstType,
+                                       nbxDevRedOpFull op, int nPreOpSrcs, ncclStream_t stream);
 
 /* Host-staged form of nbxReduceMulti: sources and destinations in HOST memory
  * (pinned for full speed; pageable works), the path NCCL's NET/SHM transports

@@ -125,6 +125,14 @@ class ReduceTask(ctypes.Structure):
                 ("count", ctypes.c_size_t)]
 
 
+class ReduceMxTask(ctypes.Structure):
+    """nbxReduceMxTask (include/nbx_reduce.h): one bucket of nbxReduceMultiWideMxBatch."""
+    _fields_ = [("dsts", ctypes.POINTER(ctypes.c_void_p)), ("dstScales", ctypes.POINTER(ctypes.c_void_p)),
+                ("nDsts", ctypes.c_int),
+                ("srcs", ctypes.POINTER(ctypes.c_void_p)), ("srcScales", ctypes.POINTER(ctypes.c_void_p)),
+                ("nSrcs", ctypes.c_int), ("count", ctypes.c_size_t)]
+
+
 class WideStats(ctypes.Structure):
     """nbxWideStats (include/nbx_reduce.h): a bucket's statistics, 16 bytes of device memory."""
     _fields_ = [("sumSq", ctypes.c_double), ("amax", ctypes.c_float), ("reserved", ctypes.c_uint32)]
@@ -182,6 +190,8 @@ _SIGS = {
     "nbxReduceMultiWideMx": [ctypes.POINTER(ctypes.c_void_p), ctypes.POINTER(ctypes.c_void_p), ctypes.c_int,
                              ctypes.POINTER(ctypes.c_void_p), ctypes.POINTER(ctypes.c_void_p), ctypes.c_int,
                              ctypes.c_size_t, ctypes.c_int, ctypes.c_int, DevRedOpFull, ctypes.c_int, ctypes.c_void_p],
+    "nbxReduceMultiWideMxBatch": [ctypes.POINTER(ReduceMxTask), ctypes.c_int, ctypes.c_int, ctypes.c_int, DevRedOpFull,
+                                  ctypes.c_int, ctypes.c_void_p],
     "nbxRedOpCreateWide": [ctypes.POINTER(ctypes.c_int), ctypes.c_int, ctypes.c_int, ctypes.c_void_p],
     "nbxSetLaunchConfig": [ctypes.c_int, ctypes.c_int],
     "nbxGetLaunchConfig": [ctypes.POINTER(ctypes.c_int), ctypes.POINTER(ctypes.c_int)],
@@ -247,6 +257,8 @@ def load_library(path: Optional[str] = None) -> ctypes.CDLL:
     lib.nbxDebugMxTileElts.restype = ctypes.c_int
     lib.nbxDebugMx4TileElts.argtypes = [ctypes.c_int, ctypes.c_int]
     lib.nbxDebugMx4TileElts.restype = ctypes.c_int
+    lib.nbxDebugMxBatchTileElts.argtypes = []
+    lib.nbxDebugMxBatchTileElts.restype = ctypes.c_int
     # test hook of the Simple transport: counters and flag words of a communicator at rest
     lib.nbxDebugSimpleState.argtypes = [ctypes.c_void_p, ctypes.POINTER(ctypes.c_uint64),
                                         ctypes.POINTER(ctypes.c_uint64), ctypes.c_size_t, ctypes.POINTER(ctypes.c_int)]
@@ -385,11 +397,12 @@ class LaunchFamily(enum.IntEnum):        # include/nbx_debug.h nbxDebugLaunchLog
     MxGeneric = 18        # ... any alignment, one element per lane (kMxGeneric)
     Mx4Blocks = 19        # its MXFP4 forms: a lane quad per block (kMx4Blocks)
     Mx4Generic = 20       # ... any alignment, one FP4 byte per lane (kMx4Generic)
+    MxBatchList = 21      # nbxReduceMultiWideMxBatch launches (kMxBatchList): flags as 15, and LAUNCH_MX_SCALED
 
 
 LAUNCH_DYNAMIC, LAUNCH_OUT32, LAUNCH_PART_FIRST = 1, 2, 4
 LAUNCH_STATS = 8   # wide families 6 / 7 / 15 / 16: the STATS form ran (nbxReduceMultiWideStats)
-LAUNCH_MX_SCALED = 16   # MX families 17 - 20: the sources carry block scales
+LAUNCH_MX_SCALED = 16   # MX families 17 - 21: the sources carry block scales
 WIDE_STATS_L = 32  # fp32 roundings into one fp64 partial: sumSq is exact within L * 2^-24 (include/nbx_reduce.h)
 LAUNCH_CHECKED, LAUNCH_SEGS_SHIFT = 1, 8   # collective families: checking instantiation, group segments (batch: buckets)
 LAUNCH_LOG_CAP = 64
@@ -555,6 +568,42 @@ def reduce_multi_batch_raw(buckets: Sequence[tuple], dtype: int, op: DevRedOpFul
     tasks, _keep = _reduce_tasks(buckets)
     return load_library().nbxReduceMultiBatch(tasks, len(buckets), int(dtype), op, int(n_pre_op_srcs),
                                               int(bool(post_op)), ctypes.c_void_p(int(stream)))
+
+
+def _reduce_mx_tasks(buckets: Sequence[tuple]) -> tuple:
+    """(nbxReduceMxTask array, the pointer arrays it refers to) of buckets
+    [(dsts, dst_scales, srcs, src_scales, count), ...]; a scale list of None is the NULL array."""
+    keep = []
+    tasks = (ReduceMxTask * max(1, len(buckets)))()
+    as_pp = lambda a: ctypes.cast(a, ctypes.POINTER(ctypes.c_void_p))
+    for i, (dsts, dst_scales, srcs, src_scales, count) in enumerate(buckets):
+        arrays = [_ptr_array(x) for x in (dsts, dst_scales, srcs, src_scales)]
+        keep += arrays
+        d, dsc, s, ssc = (as_pp(a) for a in arrays)
+        tasks[i] = ReduceMxTask(d, dsc, len(dsts), s, ssc, len(srcs), int(count))
+    return tasks, keep
+
+
+def reduce_multi_wide_mx_batch_raw(buckets: Sequence[tuple], src_type: int, dst_type: int, op: DevRedOpFull,
+                                   n_pre_op_srcs: int = 0, stream: int = 0) -> int:
+    """Call nbxReduceMultiWideMxBatch over buckets [(dsts, dst_scales, srcs, src_scales, count), ...];
+    returns the code."""
+    tasks, _keep = _reduce_mx_tasks(buckets)
+    return load_library().nbxReduceMultiWideMxBatch(tasks, len(buckets), int(src_type), int(dst_type), op,
+                                                    int(n_pre_op_srcs), ctypes.c_void_p(int(stream)))
+
+
+def reduce_multi_wide_mx_batch(buckets: Sequence[tuple], src_type: int, dst_type: int, op: DevRedOpFull,
+                               n_pre_op_srcs: int = 0, stream: int = 0) -> None:
+    """Independent MXFP8 buckets [(dsts, dst_scales, srcs, src_scales, count), ...] as batched launches: one
+    reduce_multi_wide_mx per bucket in effect, the same bits. Every bucket has `src_scales` or none has."""
+    _check(reduce_multi_wide_mx_batch_raw(buckets, src_type, dst_type, op, n_pre_op_srcs, stream),
+           "nbxReduceMultiWideMxBatch")
+
+
+def mx_batch_tile_elts() -> int:
+    """Elements per tile of nbxReduceMultiWideMxBatch's kernel (nbxDebugMxBatchTileElts)."""
+    return int(load_library().nbxDebugMxBatchTileElts())
 
 
 def reduce_multi_wide_batch_raw(buckets: Sequence[tuple], src_type: int, dst_type: int, op: DevRedOpFull,

@@ -177,6 +177,30 @@ struct MxSet {
   int valid;
 };
 
+// Its work-list batch (nbx_mx_batch.h, nbxReduceMultiWideMxBatch):
+// kMxBatchList takes BatchListArgs as it is and one tile shape for every
+// source type and count — one group per lane, kBlock groups, 128 blocks. A
+// record in the arena slot, words of 8 bytes:
+//   tileBegin, tileEnd, count | nDsts << 60   (no head: blocks count from element 0)
+//   nSrcs sources, then nSrcs source-scale pointers (scaled kinds)
+//   maxD destinations, then maxD destination-scale pointers (MX output),
+//   maxD the launch's largest nDsts; unused entries 0
+// so recWords = 3 + nSrcs (1 + scaled) + maxD (1 + MX output) <= kMxBatchRecWords,
+// and a launch holds min(kListMaxRecs, slot words / recWords) records.
+constexpr int kMxBatchTileGroups = kBlock;
+constexpr int kMxBatchTileElts = kMxBatchTileGroups * kMxGroupElts;
+constexpr int kMxBatchRecWords = 3 + 2 * kMaxKSrcs + 2 * kMaxKDsts;
+constexpr int mxBatchRecWords(int nSrcs, bool scaled, int maxD, bool mxOut) {
+  return 3 + nSrcs * (scaled ? 2 : 1) + maxD * (mxOut ? 2 : 1);
+}
+
+// Its launch table, one per source kind and apart from MxSet (which stays
+// what it is): [output as MxSet::blocks][nSrcs-1].
+struct MxBatchSet {
+  const void* list[kMxOuts][kMaxKSrcs];
+  int valid;
+};
+
 // MXFP4 elements in the same call (nbx_mx4.h): two codes per byte, so a lane of
 // the block kernel holds one 8-element group (a quarter of a block: one dword
 // of codes, one dwordx4 of a 16-bit source) and a tile is mx4Unroll x kBlock

@@ -23,6 +23,19 @@ const KernelTable& table();       // nbx_reduce.cc
 const WideTable& wideTable();     // nbx_reduce_wide.cc
 const WideStatsTable& wideStatsTable();   // the STATS forms, same indices (nbx_reduce_wide.cc)
 const MxTable& mxTable();         // the MXFP8 block-scaled sums, by source kind (nbx_reduce_mx.cc)
+const MxBatchTable& mxBatchTable();   // their work-list batch kernels, same kinds (nbx_reduce_mx_batch.cc)
+// The checks of nbxReduceMultiWideMx, shared with its batch (nbx_reduce_mx.cc).
+// mxKind: the MxTable index of checked types. checkMxTypes: the types, the op
+// and its scalar, and which scale arrays the types ask for. checkMxBucket: a
+// bucket of count > 0 — NULL entries, element alignment, the overlap rules.
+// mxBlockLayout: every element pointer 16-byte aligned and every destination
+// scale pointer 4-byte aligned (the block kernels' layout).
+int mxKind(int st, bool scaled);
+ncclResult_t checkMxTypes(ncclDataType_t srcType, ncclDataType_t dstType, const nbxDevRedOpFull& op, bool scaled,
+                          bool dstScaled);
+ncclResult_t checkMxBucket(int st, int dt, void* const* dsts, void* const* dstScales, int nDsts,
+                           const void* const* srcs, const void* const* srcScales, int nSrcs, size_t count);
+bool mxBlockLayout(void* const* dsts, void* const* dstScales, int nDsts, const void* const* srcs, int nSrcs);
 // the MXFP4 forms of nbxReduceMultiWideMx: every call that names NBX_FLOAT4_E2M1 (nbx_reduce_mx4.cc)
 ncclResult_t reduceMultiWideMx4(void* const* dsts, void* const* dstScales, int nDsts, const void* const* srcs,
                                 const void* const* srcScales, int nSrcs, size_t count, ncclDataType_t srcType,
@@ -93,10 +106,11 @@ enum LaunchFamily {
   kFamWideBatchList = 15,               // the same for nbxReduceMultiWideBatch (bit 1: fp32 output)
   kFamWideShiftedLds = 16,              // wide realigning LDS-DMA (kWideShiftedLds)
   kFamMxBlocks = 17, kFamMxGeneric = 18,  // nbxReduceMultiWideMx: block kernel (kMxBlocks), any alignment (kMxGeneric)
-  kFamMx4Blocks = 19, kFamMx4Generic = 20 // its MXFP4 forms: quad layout (kMx4Blocks), any alignment (kMx4Generic)
+  kFamMx4Blocks = 19, kFamMx4Generic = 20, // its MXFP4 forms: quad layout (kMx4Blocks), any alignment (kMx4Generic)
+  kFamMxBatchList = 21                    // nbxReduceMultiWideMxBatch's work-list launches (kMxBatchList), flags as 15
 };
 // kLaunchStats: the STATS form of a wide family (6 / 7 / 15 / 16) ran
-// kLaunchMxScaled: the sources of an MX family (17 - 20) carry block scales
+// kLaunchMxScaled: the sources of an MX family (17 - 21) carry block scales
 enum LaunchFlag { kLaunchDynamic = 1, kLaunchOut32 = 2, kLaunchPartFirst = 4, kLaunchStats = 8, kLaunchMxScaled = 16 };
 void logLaunch(int family, int nSrcs, int unroll, int flags);
 
@@ -125,6 +139,17 @@ ncclResult_t wideStatsFinish(WideSlot* slots, size_t n, nbxWideStats* out, hipSt
 // The op as the wide kernels take it: their scalar is an fp32 value, and only
 // PreMulSum has one — zero without it, the low 32 bits when passed by value.
 nbxDevRedOpFull wideScalarOp(nbxDevRedOpFull op);
+
+// ---- the work-list arena (nbx_reduce_batch.cc), for every work-list launcher ----
+bool batchListEnabled();   // NBX_BATCH_LIST / nbxDebugSetBatchMode: not 0
+// A free slot of the device's arena (its index, *ptr = its kBatchListSlotBytes
+// of write-only memory), or -1: nothing ever waits for a slot.
+int acquireListSlot(int dev, bool capturing, char** ptr);
+// Makes the host's writes into the slot land before the launch; `last` is the last word written.
+void publishListSlot(int dev, const volatile uint32_t* last);
+// After the launch that reads slot i: eager -> an event frees it; captured
+// (graph != nullptr) -> the graph owns it until destroyed; not launched -> free.
+void releaseListSlot(int dev, int i, hipStream_t st, hipGraph_t graph, bool launched);
 
 // ---- rules shared by the launchers ----
 inline bool overlaps(const void* a, size_t aBytes, const void* b, size_t bBytes) {

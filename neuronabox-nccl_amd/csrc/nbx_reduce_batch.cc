@@ -143,6 +143,8 @@ bool allocArena(ListArena& A, int dev) {
   return true;
 }
 
+}  // namespace
+
 // A free slot of this device's arena (index, *ptr = its memory), or -1.
 int acquireListSlot(int dev, bool capturing, char** ptr) {
   if (dev < 0 || dev >= kMaxDevices) return -1;
@@ -214,6 +216,7 @@ void releaseListSlot(int dev, int i, hipStream_t st, hipGraph_t graph, bool laun
   A.state[i].store(1);
 }
 
+namespace {
 // NBX_BATCH_LIST: 1 (default) = work-list launches (sets of <= 16 buckets
 // that fit one kernel-argument table excepted), 2 = work lists for every set,
 // 0 = kernel-argument batches only (also settable through nbxDebugSetBatchMode).
@@ -222,7 +225,9 @@ int parseBatchMode() {
   return e == 0 ? 0 : (e == 2 ? 2 : 1);
 }
 LazySetting<int> g_batchMode{-1, parseBatchMode};
+}  // namespace
 bool batchListEnabled() { return g_batchMode.get() != 0; }
+namespace {
 
 // Launches the buckets of one source count as work-list kernels (as many
 // launches as slots they need). Returns the number of buckets launched from

@@ -14,11 +14,7 @@ std::once_flag g_mxOnce;
 
 bool isFp8(int t) { return t == (int)ncclFloat8e4m3 || t == (int)ncclFloat8e5m2; }
 
-// Source kind (MxTable index) and output index (MxSet::blocks) of checked types.
-int mxKind(int st, bool scaled) {
-  const int plain = st == (int)ncclFloat16 ? 0 : st == (int)ncclBfloat16 ? 1 : st == (int)ncclFloat8e4m3 ? 2 : 3;
-  return scaled ? plain + 2 : plain;
-}
+// Output index (MxSet::blocks) of a checked type.
 int mxOut(int dt) { return dt == (int)ncclFloat8e4m3 ? 0 : dt == (int)ncclFloat8e5m2 ? 1 : 2; }
 
 struct MxCall {
@@ -79,6 +75,61 @@ ncclResult_t launchMxPass(const MxCall& c, int out, bool partFirst, void* const*
 bool aligned(const void* p, unsigned a) { return ((uintptr_t)p & (a - 1u)) == 0; }
 }  // namespace
 
+// Source kind (MxTable index) of checked types.
+int mxKind(int st, bool scaled) {
+  const int plain = st == (int)ncclFloat16 ? 0 : st == (int)ncclBfloat16 ? 1 : st == (int)ncclFloat8e4m3 ? 2 : 3;
+  return scaled ? plain + 2 : plain;
+}
+
+// The four source types, Sum / PreMulSum, the scalar; scales only beside fp8
+// sources; an fp8 output with scale arrays, or fp32 without and from scaled
+// sources only.
+ncclResult_t checkMxTypes(ncclDataType_t srcType, ncclDataType_t dstType, const nbxDevRedOpFull& op, bool scaled,
+                          bool dstScaled) {
+  ncclResult_t cr = checkWideOp(srcType, srcType, op);
+  if (cr != ncclSuccess) return cr;
+  const int st = (int)srcType, dt = (int)dstType;
+  if (scaled && !isFp8(st)) return ncclInvalidArgument;
+  if (dt == (int)ncclFloat32 ? (dstScaled || !scaled) : (!isFp8(dt) || !dstScaled)) return ncclInvalidArgument;
+  return ncclSuccess;
+}
+
+ncclResult_t checkMxBucket(int st, int dt, void* const* dsts, void* const* dstScales, int nDsts,
+                           const void* const* srcs, const void* const* srcScales, int nSrcs, size_t count) {
+  const bool scaled = srcScales != nullptr, out32 = dt == (int)ncclFloat32;
+  const size_t eb = (size_t)typeSize(st), deb = out32 ? sizeof(float) : 1;
+  if (!pointersOk(eb, deb, dsts, nDsts, srcs, nSrcs)) return ncclInvalidArgument;
+  for (int s = 0; scaled && s < nSrcs; s++)
+    if (srcScales[s] == nullptr) return ncclInvalidArgument;
+  for (int d = 0; !out32 && d < nDsts; d++)
+    if (dstScales[d] == nullptr) return ncclInvalidArgument;
+  // A destination may be one of the sources when the types agree (a lane
+  // reads the bytes it writes before it writes them), and its scales then are
+  // that source's; everything else a destination owns is apart from
+  // everything a source owns, and its two arrays from each other.
+  const size_t nScales = (count + kMxBlockElts - 1) / kMxBlockElts;
+  for (int d = 0; d < nDsts; d++) {
+    if (!out32 && overlaps(dsts[d], count * deb, dstScales[d], nScales)) return ncclInvalidArgument;
+    for (int s = 0; s < nSrcs; s++) {
+      const bool same = st == dt && dsts[d] == srcs[s];
+      if (!same && overlaps(dsts[d], count * deb, srcs[s], count * eb)) return ncclInvalidArgument;
+      if (same && scaled && dstScales[d] != srcScales[s]) return ncclInvalidArgument;
+      if (scaled && overlaps(dsts[d], count * deb, srcScales[s], nScales)) return ncclInvalidArgument;
+      if (out32) continue;
+      if (overlaps(dstScales[d], nScales, srcs[s], count * eb)) return ncclInvalidArgument;
+      if (scaled && !same && overlaps(dstScales[d], nScales, srcScales[s], nScales)) return ncclInvalidArgument;
+    }
+  }
+  return ncclSuccess;
+}
+
+bool mxBlockLayout(void* const* dsts, void* const* dstScales, int nDsts, const void* const* srcs, int nSrcs) {
+  bool ok = true;
+  for (int s = 0; s < nSrcs; s++) ok &= aligned(srcs[s], 16);
+  for (int d = 0; d < nDsts; d++) ok &= aligned(dsts[d], 16) && (dstScales == nullptr || aligned(dstScales[d], 4));
+  return ok;
+}
+
 const MxTable& mxTable() {
   std::call_once(g_mxOnce, [] {
     std::memset(&g_mx, 0, sizeof(g_mx));
@@ -105,37 +156,14 @@ NBX_EXPORT ncclResult_t nbxReduceMultiWideMx(void* const* dsts, void* const* dst
                               stream);
   // ---- checks: all of them before any device call ----
   if (!argArraysOk(dsts, nDsts, srcs, nSrcs)) return ncclInvalidArgument;
-  ncclResult_t cr = checkWideOp(srcType, srcType, op);   // the four source types, Sum / PreMulSum, the scalar
-  if (cr != ncclSuccess) return cr;
-  const int st = (int)srcType, dt = (int)dstType;
   const bool scaled = srcScales != nullptr;
-  if (scaled && !isFp8(st)) return ncclInvalidArgument;
-  const bool out32 = dt == (int)ncclFloat32;
-  if (out32 ? (dstScales != nullptr || !scaled) : (!isFp8(dt) || dstScales == nullptr)) return ncclInvalidArgument;
+  ncclResult_t cr = checkMxTypes(srcType, dstType, op, scaled, dstScales != nullptr);
+  if (cr != ncclSuccess) return cr;
   if (count == 0) return ncclSuccess;
-  const size_t eb = (size_t)typeSize(st), deb = out32 ? sizeof(float) : 1;
-  if (!pointersOk(eb, deb, dsts, nDsts, srcs, nSrcs)) return ncclInvalidArgument;
-  for (int s = 0; scaled && s < nSrcs; s++)
-    if (srcScales[s] == nullptr) return ncclInvalidArgument;
-  for (int d = 0; !out32 && d < nDsts; d++)
-    if (dstScales[d] == nullptr) return ncclInvalidArgument;
-  // A destination may be one of the sources when the types agree (a lane
-  // reads the bytes it writes before it writes them), and its scales then are
-  // that source's; everything else a destination owns is apart from
-  // everything a source owns, and its two arrays from each other.
-  const size_t nScales = (count + kMxBlockElts - 1) / kMxBlockElts;
-  for (int d = 0; d < nDsts; d++) {
-    if (!out32 && overlaps(dsts[d], count * deb, dstScales[d], nScales)) return ncclInvalidArgument;
-    for (int s = 0; s < nSrcs; s++) {
-      const bool same = st == dt && dsts[d] == srcs[s];
-      if (!same && overlaps(dsts[d], count * deb, srcs[s], count * eb)) return ncclInvalidArgument;
-      if (same && scaled && dstScales[d] != srcScales[s]) return ncclInvalidArgument;
-      if (scaled && overlaps(dsts[d], count * deb, srcScales[s], nScales)) return ncclInvalidArgument;
-      if (out32) continue;
-      if (overlaps(dstScales[d], nScales, srcs[s], count * eb)) return ncclInvalidArgument;
-      if (scaled && !same && overlaps(dstScales[d], nScales, srcScales[s], nScales)) return ncclInvalidArgument;
-    }
-  }
+  const int st = (int)srcType, dt = (int)dstType;
+  const bool out32 = dt == (int)ncclFloat32;
+  cr = checkMxBucket(st, dt, dsts, dstScales, nDsts, srcs, srcScales, nSrcs, count);
+  if (cr != ncclSuccess) return cr;
 
   // ---- layout: the block kernel needs 16-byte element pointers and 4-byte
   // destination scale pointers (the partial, scratch or dsts[0], follows) ----
@@ -147,9 +175,7 @@ NBX_EXPORT ncclResult_t nbxReduceMultiWideMx(void* const* dsts, void* const* dst
   c.srcScales = srcScales;
   c.op = wideScalarOp(op);
   c.stream = (hipStream_t)stream;
-  c.blocks = true;
-  for (int s = 0; s < nSrcs; s++) c.blocks &= aligned(srcs[s], 16);
-  for (int d = 0; d < nDsts; d++) c.blocks &= aligned(dsts[d], 16) && (out32 || aligned(dstScales[d], 4));
+  c.blocks = mxBlockLayout(dsts, out32 ? nullptr : dstScales, nDsts, srcs, nSrcs);
   if (nPreOpSrcs < 0) nPreOpSrcs = 0;
   const bool pre = op.op == nbxDevPreMulSum;
 

@@ -60,6 +60,16 @@ void fillMxE5M2(MxTable& t);
 void fillMxE4M3Scaled(MxTable& t);
 void fillMxE5M2Scaled(MxTable& t);
 
+// their work-list batch (nbxReduceMultiWideMxBatch, nbx_mx_batch.h): one
+// MxBatchSet per source kind, a unit per kind (inst_mxb_*.hip)
+typedef MxBatchSet MxBatchTable[kMxKinds];
+void fillMxBatchF16(MxBatchTable& t);
+void fillMxBatchBF16(MxBatchTable& t);
+void fillMxBatchE4M3(MxBatchTable& t);
+void fillMxBatchE5M2(MxBatchTable& t);
+void fillMxBatchE4M3Scaled(MxBatchTable& t);
+void fillMxBatchE5M2Scaled(MxBatchTable& t);
+
 // its MXFP4 forms (NBX_FLOAT4_E2M1, nbx_mx4.h): one Mx4Set per source kind, a
 // unit per kind (inst_mx4_*.hip)
 typedef Mx4Set Mx4Table[kMx4Kinds];
