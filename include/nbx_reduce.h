@@ -347,12 +347,52 @@ ncclResult_t nbxReduceMultiWideBatchStats(const nbxReduceTask* tasks, int nTasks
  * MXFP4 into MXFP4, on the source's own scale array. The block kernel (a lane
  * quad per block) needs the same alignments; any other layout runs one FP4
  * byte per lane. Same bits.
- * Not provided (ncclInvalidArgument): MXFP6; fp8 sources, plain or MX, into
+ *
+ * MXFP6 (OCP E2M3 / E3M2) elements: NBX_FLOAT6_E2M3 or NBX_FLOAT6_E3M2 as
+ * srcType, dstType or both, tags only this function accepts. A code is 6 bits,
+ * a sign in bit 5 over a 5-bit magnitude; neither type has an inf or NaN code.
+ *   E2M3: exponent in bits 4:3 (bias 1), mantissa m in bits 2:0. Exponent
+ *     field 0: m / 8; else (1 + m / 8) * 2^(e - 1). Largest 7.5 (0x1F), emax 2.
+ *   E3M2: exponent in bits 4:2 (bias 3), mantissa m in bits 1:0. Exponent
+ *     field 0: m / 16; else (1 + m / 4) * 2^(e - 3). Largest 28 (0x1F), emax 4.
+ * An FP6 buffer is a dense little-endian bit stream of ceil(3 * count / 4)
+ * bytes: element i occupies bits [6 i, 6 i + 6), so four elements c0..c3 are
+ * the three bytes b0 = c0 | c1 << 6, b1 = c1 >> 2 | c2 << 4, b2 = c2 >> 4 |
+ * c3 << 2 (each truncated to 8 bits). Element 0 starts at bit 0, so the pointer
+ * is byte-aligned. The unused high bits of a destination's last byte are
+ * stored as 0, those of a source's last byte are ignored. Blocks and scale
+ * arrays are as above: block b is elements [32 b, 32 b + 32), 24 bytes when
+ * full, and a scale array has ceil(count / 32) bytes.
+ *   ncclFloat16 / ncclBfloat16 sources (srcScales NULL) into MXFP6 of either
+ *     type (dstScales given);
+ *   MXFP6 sources (srcScales and every entry non-NULL) into MXFP6 of the same
+ *     type, or into fp32 (dstScales NULL).
+ * An MXFP6 source element is f32(code) * X with the X above (one fp32
+ * multiply; a 0xFF block is NaN), the PreMulSum multiply after it. The fold is
+ * the same. MXFP6 output follows the MX output rule with the type's emax (2
+ * for E2M3, 4 for E3M2): for finite m, S = max(be - emax, 0), R = 2^(127 - S),
+ * and element i is narrow6(a_i * R): one fp32 multiply, then
+ * round-to-nearest-even onto the type's grid, subnormals included. Every
+ * magnitude above the largest stores the largest, a tie that would round up
+ * past it too: E2M3 everything above 7.5, so (7.5, 8) saturates; E3M2
+ * everything above 28, so (28, 32) saturates. The sign is kept: -0 is 0x20,
+ * and magnitudes that round to zero keep their sign. For a non-finite m the
+ * scale byte is 0xFF and EVERY code of the block is 0, as for MXFP4. The stored
+ * bits are a function of the arguments alone, whichever kernel runs.
+ * Overlap as above with ceil(3 * count / 4) as an FP6 array's size; in place
+ * only MXFP6 into the same type, on the source's own scale array. count == 0
+ * is a no-op after the type and op checks. The block kernel (a block per lane
+ * at the converters, nbx_mx6.h) needs the same alignments; any other layout
+ * runs four elements (three bytes) per lane. Same bits.
+ * Not provided (ncclInvalidArgument): E2M3 <-> E3M2, FP6 <-> FP8 / FP4 pairs;
+ * FP6 sources without scales; fp8 sources, plain or MX, into
  * MXFP4; MXFP4 sources into MXFP8; MXFP4 sources without scales; block sizes
- * other than 32; a batched form of MXFP4 (MXFP8 has one:
+ * other than 32; a batched form of MXFP4 or MXFP6 (MXFP8 has one:
  * nbxReduceMultiWideMxBatch), a statistics form, a form inside the
  * collectives, a host-staged form, a realigning LDS-DMA form. */
 #define NBX_FLOAT4_E2M1 ((ncclDataType_t)32)
+#define NBX_FLOAT6_E2M3 ((ncclDataType_t)33)
+#define NBX_FLOAT6_E3M2 ((ncclDataType_t)34)
 ncclResult_t nbxReduceMultiWideMx(void* const* dsts, void* const* dstScales, int nDsts,
                                   const void* const* srcs, const void* const* srcScales, int nSrcs,
                                   size_t count, ncclDataType_t srcType, ncclDataType_t dstType,

@@ -257,6 +257,8 @@ def load_library(path: Optional[str] = None) -> ctypes.CDLL:
     lib.nbxDebugMxTileElts.restype = ctypes.c_int
     lib.nbxDebugMx4TileElts.argtypes = [ctypes.c_int, ctypes.c_int]
     lib.nbxDebugMx4TileElts.restype = ctypes.c_int
+    lib.nbxDebugMx6TileElts.argtypes = [ctypes.c_int, ctypes.c_int]
+    lib.nbxDebugMx6TileElts.restype = ctypes.c_int
     lib.nbxDebugMxBatchTileElts.argtypes = []
     lib.nbxDebugMxBatchTileElts.restype = ctypes.c_int
     # test hook of the Simple transport: counters and flag words of a communicator at rest
@@ -398,11 +400,13 @@ class LaunchFamily(enum.IntEnum):        # include/nbx_debug.h nbxDebugLaunchLog
     Mx4Blocks = 19        # its MXFP4 forms: a lane quad per block (kMx4Blocks)
     Mx4Generic = 20       # ... any alignment, one FP4 byte per lane (kMx4Generic)
     MxBatchList = 21      # nbxReduceMultiWideMxBatch launches (kMxBatchList): flags as 15, and LAUNCH_MX_SCALED
+    Mx6Blocks = 22        # nbxReduceMultiWideMx's MXFP6 forms: a block per lane at the converters (kMx6Blocks)
+    Mx6Generic = 23       # ... any alignment, four elements (three bytes) per lane (kMx6Generic)
 
 
 LAUNCH_DYNAMIC, LAUNCH_OUT32, LAUNCH_PART_FIRST = 1, 2, 4
 LAUNCH_STATS = 8   # wide families 6 / 7 / 15 / 16: the STATS form ran (nbxReduceMultiWideStats)
-LAUNCH_MX_SCALED = 16   # MX families 17 - 21: the sources carry block scales
+LAUNCH_MX_SCALED = 16   # MX families 17 - 23: the sources carry block scales
 WIDE_STATS_L = 32  # fp32 roundings into one fp64 partial: sumSq is exact within L * 2^-24 (include/nbx_reduce.h)
 LAUNCH_CHECKED, LAUNCH_SEGS_SHIFT = 1, 8   # collective families: checking instantiation, group segments (batch: buckets)
 LAUNCH_LOG_CAP = 64
@@ -490,6 +494,7 @@ def reduce_multi_wide_stats(dsts: Sequence[int], srcs: Sequence[int], count: int
 
 MX_BLOCK = 32   # elements per MX block: one E8M0 scale byte each (include/nbx_reduce.h)
 FLOAT4_E2M1 = 32   # NBX_FLOAT4_E2M1: MXFP4 elements, two codes per byte; reduce_multi_wide_mx alone takes it
+FLOAT6_E2M3, FLOAT6_E3M2 = 33, 34   # NBX_FLOAT6_*: MXFP6 elements, a dense stream of 6-bit codes; the same
 
 
 def _ptr_array(ptrs: Optional[Sequence[int]]):
@@ -513,7 +518,9 @@ def reduce_multi_wide_mx(dsts: Sequence[int], dst_scales: Optional[Sequence[int]
     """reduce_multi_wide with MXFP8 on either side: `dst_scales` (one byte per 32 elements beside each
     fp8 destination) for a block-scaled output, `src_scales` for block-scaled fp8 sources; with
     `src_scales` the output may also be fp32 (`dst_scales` None). FLOAT4_E2M1 as either type: MXFP4,
-    two codes per byte (f16 / bf16 or MXFP4 sources into MXFP4; MXFP4 sources into fp32)."""
+    two codes per byte (f16 / bf16 or MXFP4 sources into MXFP4; MXFP4 sources into fp32). FLOAT6_E2M3 /
+    FLOAT6_E3M2: MXFP6, 6-bit codes as a dense little-endian bit stream of ceil(3 * count / 4) bytes
+    (f16 / bf16 sources into either type; MXFP6 sources into the same type or fp32)."""
     _check(reduce_multi_wide_mx_raw(dsts, dst_scales, srcs, src_scales, count, src_type, dst_type, op, n_pre_op_srcs,
                                     stream), "nbxReduceMultiWideMx")
 
@@ -521,6 +528,11 @@ def reduce_multi_wide_mx(dsts: Sequence[int], dst_scales: Optional[Sequence[int]
 def mx_tile_elts(src_type: int, n_srcs: int) -> int:
     """Elements per tile of nbxReduceMultiWideMx's block kernel (nbxDebugMxTileElts)."""
     return int(load_library().nbxDebugMxTileElts(int(src_type), int(n_srcs)))
+
+
+def mx6_tile_elts(src_type: int, n_srcs: int) -> int:
+    """Elements per tile of the MXFP6 block kernel (nbxDebugMx6TileElts)."""
+    return int(load_library().nbxDebugMx6TileElts(int(src_type), int(n_srcs)))
 
 
 def mx4_tile_elts(src_type: int, n_srcs: int) -> int:

@@ -220,6 +220,25 @@ struct Mx4Set {
   int valid;
 };
 
+// MXFP6 elements in the same call (nbx_mx6.h): 6-bit codes in a dense bit stream,
+// 24 bytes per block. gfx950's FP6 converters take a whole block in one lane, so
+// the block kernel's unit is the block: a lane ends up owning mx6Unroll blocks
+// per tile (a tile is mx6Unroll x kBlock blocks). A 16-bit source brings 64 bytes
+// per lane and block, an MXFP6 source 24.
+constexpr int kTypeFp6E2M3 = 33, kTypeFp6E3M2 = 34;   // NBX_FLOAT6_E2M3 / NBX_FLOAT6_E3M2 (include/nbx_reduce.h)
+constexpr int mx6Unroll(int nSrcs, bool fp6) { return fp6 ? (nSrcs <= 4 ? 4 : 2) : (nSrcs <= 3 ? 2 : 1); }
+
+// Launch table of one source kind: f16, bf16 plain, E2M3, E3M2. [output: plain
+// kinds 0 E2M3, 1 E3M2; MXFP6 kinds 0 their own type, 1 fp32][source 0 is an
+// fp32 partial][nSrcs-1].
+constexpr int kMx6Kinds = 4;
+struct Mx6Set {
+  const void* blocks[2][2][kMaxKSrcs];
+  const void* generic[2][2];
+  int fp6;
+  int valid;
+};
+
 // Bucket statistics of the fp32-accumulating sums (nbxReduceMultiWideStats,
 // nbx_wide.h "Bucket statistics"). The STATS kernels take the slot array as a
 // second kernel argument, so KArgs and BatchListArgs are what they were.

@@ -40,6 +40,10 @@ bool mxBlockLayout(void* const* dsts, void* const* dstScales, int nDsts, const v
 ncclResult_t reduceMultiWideMx4(void* const* dsts, void* const* dstScales, int nDsts, const void* const* srcs,
                                 const void* const* srcScales, int nSrcs, size_t count, ncclDataType_t srcType,
                                 ncclDataType_t dstType, nbxDevRedOpFull op, int nPreOpSrcs, ncclStream_t stream);
+// the MXFP6 forms: every call that names NBX_FLOAT6_E2M3 or NBX_FLOAT6_E3M2 (nbx_reduce_mx6.cc)
+ncclResult_t reduceMultiWideMx6(void* const* dsts, void* const* dstScales, int nDsts, const void* const* srcs,
+                                const void* const* srcScales, int nSrcs, size_t count, ncclDataType_t srcType,
+                                ncclDataType_t dstType, nbxDevRedOpFull op, int nPreOpSrcs, ncclStream_t stream);
 int typeSize(int dt);             // bytes of an ncclDataType_t, -1 unknown (nbx_reduce.cc)
 
 // ---- launch policy, device and stream helpers (nbx_policy.cc) ----
@@ -107,10 +111,11 @@ enum LaunchFamily {
   kFamWideShiftedLds = 16,              // wide realigning LDS-DMA (kWideShiftedLds)
   kFamMxBlocks = 17, kFamMxGeneric = 18,  // nbxReduceMultiWideMx: block kernel (kMxBlocks), any alignment (kMxGeneric)
   kFamMx4Blocks = 19, kFamMx4Generic = 20, // its MXFP4 forms: quad layout (kMx4Blocks), any alignment (kMx4Generic)
-  kFamMxBatchList = 21                    // nbxReduceMultiWideMxBatch's work-list launches (kMxBatchList), flags as 15
+  kFamMxBatchList = 21,                   // nbxReduceMultiWideMxBatch's work-list launches (kMxBatchList), flags as 15
+  kFamMx6Blocks = 22, kFamMx6Generic = 23 // the MXFP6 forms: a block per lane (kMx6Blocks), any alignment (kMx6Generic)
 };
 // kLaunchStats: the STATS form of a wide family (6 / 7 / 15 / 16) ran
-// kLaunchMxScaled: the sources of an MX family (17 - 21) carry block scales
+// kLaunchMxScaled: the sources of an MX family (17 - 23) carry block scales
 enum LaunchFlag { kLaunchDynamic = 1, kLaunchOut32 = 2, kLaunchPartFirst = 4, kLaunchStats = 8, kLaunchMxScaled = 16 };
 void logLaunch(int family, int nSrcs, int unroll, int flags);
 

@@ -151,6 +151,10 @@ NBX_EXPORT ncclResult_t nbxReduceMultiWideMx(void* const* dsts, void* const* dst
                                              const void* const* srcs, const void* const* srcScales, int nSrcs,
                                              size_t count, ncclDataType_t srcType, ncclDataType_t dstType,
                                              nbxDevRedOpFull op, int nPreOpSrcs, ncclStream_t stream) {
+  const auto fp6 = [](ncclDataType_t t) { return (int)t == kTypeFp6E2M3 || (int)t == kTypeFp6E3M2; };
+  if (fp6(srcType) || fp6(dstType))   // MXFP6: nbx_reduce_mx6.cc; a pair with NBX_FLOAT4_E2M1 is refused there
+    return reduceMultiWideMx6(dsts, dstScales, nDsts, srcs, srcScales, nSrcs, count, srcType, dstType, op, nPreOpSrcs,
+                              stream);
   if ((int)srcType == kTypeFp4 || (int)dstType == kTypeFp4)   // MXFP4: nbx_reduce_mx4.cc
     return reduceMultiWideMx4(dsts, dstScales, nDsts, srcs, srcScales, nSrcs, count, srcType, dstType, op, nPreOpSrcs,
                               stream);

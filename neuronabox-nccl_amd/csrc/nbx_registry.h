@@ -76,4 +76,12 @@ typedef Mx4Set Mx4Table[kMx4Kinds];
 void fillMx4F16(Mx4Table& t);
 void fillMx4BF16(Mx4Table& t);
 void fillMx4Fp4(Mx4Table& t);
+
+// its MXFP6 forms (NBX_FLOAT6_E2M3 / NBX_FLOAT6_E3M2, nbx_mx6.h): one Mx6Set per
+// source kind, a unit per kind (inst_mx6_*.hip)
+typedef Mx6Set Mx6Table[kMx6Kinds];
+void fillMx6F16(Mx6Table& t);
+void fillMx6BF16(Mx6Table& t);
+void fillMx6E2M3(Mx6Table& t);
+void fillMx6E3M2(Mx6Table& t);
 }  // namespace nbx
