@@ -311,7 +311,7 @@ int nbxDebugMxTileElts(ncclDataType_t srcType, int nSrcs);
  * NBX_FLOAT4_E2M1. */
 int nbxDebugMx4TileElts(ncclDataType_t srcType, int nSrcs);
 /* The same for the MXFP6 block kernel: srcType ncclFloat16, ncclBfloat16,
- * NBX_FLOAT6_E2M3 or NBX_FLOAT6_E3M2. Its launches (nbx_reduce_mx6.cc) leave
+ * NBX_FLOAT6_E2M3 or NBX_FLOAT6_E3M2. Its launches (nbx_reduce_mx.cc) leave
  * records of family 22 (kMx6Blocks: a block per lane; unroll: the blocks a
  * lane owns per tile) and 23 (kMx6Generic: any alignment, four elements per
  * lane; unroll 1), flags as for 19 / 20, bit 4 set for MXFP6 sources. */

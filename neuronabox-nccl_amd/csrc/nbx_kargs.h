@@ -165,17 +165,29 @@ struct MxArgs {
   uint8_t* dstScale[kMaxKDsts];         // fp8 outputs only
 };
 
-// Launch table of one source kind: f16, bf16, e4m3, e5m2 plain, e4m3 / e5m2
-// with scales. [output: 0 e4m3, 1 e5m2, 2 fp32 (scaled kinds only)][source 0
-// is an fp32 partial][nSrcs-1]; the generic kernel takes nSrcs at run time.
-constexpr int kMxKinds = 6, kMxOuts = 3;
+// Launch table of one source kind of nbxReduceMultiWideMx, the same struct for
+// every element format (the kinds and their outputs: nbx_registry.h MxTable).
+// [output][source 0 is an fp32 partial][nSrcs-1]; the generic kernel takes
+// nSrcs at run time. An output a kind does not have stays NULL.
+constexpr int kMxKinds = 13, kMxOuts = 3;
+constexpr int kMxFp8Kinds = 6;   // the MXFP8 kinds come first; the batch has these alone
 struct MxSet {
   const void* blocks[kMxOuts][2][kMaxKSrcs];
   const void* generic[kMxOuts][2];
-  int eltBytes;
-  int scaled;
+  int scaled;   // the sources carry block scales
   int valid;
 };
+// One output of a set: the block kernels of 1 .. 8 sources, those behind a
+// partial (later[0] is NULL: a partial alone is no pass), the generic pair.
+inline void setMxOut(MxSet& ms, int out, const void* const* first, const void* const* later, const void* generic,
+                     const void* genericPart) {
+  for (int i = 0; i < kMaxKSrcs; i++) {
+    ms.blocks[out][0][i] = first[i];
+    ms.blocks[out][1][i] = later[i];
+  }
+  ms.generic[out][0] = generic;
+  ms.generic[out][1] = genericPart;
+}
 
 // Its work-list batch (nbx_mx_batch.h, nbxReduceMultiWideMxBatch):
 // kMxBatchList takes BatchListArgs as it is and one tile shape for every
@@ -194,8 +206,7 @@ constexpr int mxBatchRecWords(int nSrcs, bool scaled, int maxD, bool mxOut) {
   return 3 + nSrcs * (scaled ? 2 : 1) + maxD * (mxOut ? 2 : 1);
 }
 
-// Its launch table, one per source kind and apart from MxSet (which stays
-// what it is): [output as MxSet::blocks][nSrcs-1].
+// Its launch table, one per MXFP8 source kind: [output as MxSet::blocks][nSrcs-1].
 struct MxBatchSet {
   const void* list[kMxOuts][kMaxKSrcs];
   int valid;
@@ -210,16 +221,6 @@ constexpr int kMx4GroupElts = 8;
 constexpr int kTypeFp4 = 32;   // NBX_FLOAT4_E2M1 (include/nbx_reduce.h): a tag outside ncclDataType_t's own values
 constexpr int mx4Unroll(int nSrcs, bool fp4) { return fp4 ? (nSrcs <= 4 ? 8 : 4) : (nSrcs >= 4 ? 4 : 2); }
 
-// Launch table of one source kind: f16, bf16 plain, MXFP4. [output: 0 MXFP4,
-// 1 fp32 (MXFP4 sources only)][source 0 is an fp32 partial][nSrcs-1].
-constexpr int kMx4Kinds = 3;
-struct Mx4Set {
-  const void* blocks[2][2][kMaxKSrcs];
-  const void* generic[2][2];
-  int fp4;
-  int valid;
-};
-
 // MXFP6 elements in the same call (nbx_mx6.h): 6-bit codes in a dense bit stream,
 // 24 bytes per block. gfx950's FP6 converters take a whole block in one lane, so
 // the block kernel's unit is the block: a lane ends up owning mx6Unroll blocks
@@ -227,17 +228,6 @@ struct Mx4Set {
 // per lane and block, an MXFP6 source 24.
 constexpr int kTypeFp6E2M3 = 33, kTypeFp6E3M2 = 34;   // NBX_FLOAT6_E2M3 / NBX_FLOAT6_E3M2 (include/nbx_reduce.h)
 constexpr int mx6Unroll(int nSrcs, bool fp6) { return fp6 ? (nSrcs <= 4 ? 4 : 2) : (nSrcs <= 3 ? 2 : 1); }
-
-// Launch table of one source kind: f16, bf16 plain, E2M3, E3M2. [output: plain
-// kinds 0 E2M3, 1 E3M2; MXFP6 kinds 0 their own type, 1 fp32][source 0 is an
-// fp32 partial][nSrcs-1].
-constexpr int kMx6Kinds = 4;
-struct Mx6Set {
-  const void* blocks[2][2][kMaxKSrcs];
-  const void* generic[2][2];
-  int fp6;
-  int valid;
-};
 
 // Bucket statistics of the fp32-accumulating sums (nbxReduceMultiWideStats,
 // nbx_wide.h "Bucket statistics"). The STATS kernels take the slot array as a

@@ -22,28 +22,20 @@ namespace nbx {
 const KernelTable& table();       // nbx_reduce.cc
 const WideTable& wideTable();     // nbx_reduce_wide.cc
 const WideStatsTable& wideStatsTable();   // the STATS forms, same indices (nbx_reduce_wide.cc)
-const MxTable& mxTable();         // the MXFP8 block-scaled sums, by source kind (nbx_reduce_mx.cc)
-const MxBatchTable& mxBatchTable();   // their work-list batch kernels, same kinds (nbx_reduce_mx_batch.cc)
+const MxTable& mxTable();         // the block-scaled sums, by source kind (nbx_reduce_mx.cc)
+const MxBatchTable& mxBatchTable();   // the MXFP8 kinds' work-list batch kernels (nbx_reduce_mx_batch.cc)
 // The checks of nbxReduceMultiWideMx, shared with its batch (nbx_reduce_mx.cc).
-// mxKind: the MxTable index of checked types. checkMxTypes: the types, the op
-// and its scalar, and which scale arrays the types ask for. checkMxBucket: a
+// checkMxTypes: the types, the op and its scalar, and which scale arrays the
+// types ask for, against the format table; *kind is then the MxTable index of
+// the sources and *out the MxSet::blocks index of the output. checkMxBucket: a
 // bucket of count > 0 — NULL entries, element alignment, the overlap rules.
 // mxBlockLayout: every element pointer 16-byte aligned and every destination
 // scale pointer 4-byte aligned (the block kernels' layout).
-int mxKind(int st, bool scaled);
 ncclResult_t checkMxTypes(ncclDataType_t srcType, ncclDataType_t dstType, const nbxDevRedOpFull& op, bool scaled,
-                          bool dstScaled);
+                          bool dstScaled, int* kind, int* out);
 ncclResult_t checkMxBucket(int st, int dt, void* const* dsts, void* const* dstScales, int nDsts,
                            const void* const* srcs, const void* const* srcScales, int nSrcs, size_t count);
 bool mxBlockLayout(void* const* dsts, void* const* dstScales, int nDsts, const void* const* srcs, int nSrcs);
-// the MXFP4 forms of nbxReduceMultiWideMx: every call that names NBX_FLOAT4_E2M1 (nbx_reduce_mx4.cc)
-ncclResult_t reduceMultiWideMx4(void* const* dsts, void* const* dstScales, int nDsts, const void* const* srcs,
-                                const void* const* srcScales, int nSrcs, size_t count, ncclDataType_t srcType,
-                                ncclDataType_t dstType, nbxDevRedOpFull op, int nPreOpSrcs, ncclStream_t stream);
-// the MXFP6 forms: every call that names NBX_FLOAT6_E2M3 or NBX_FLOAT6_E3M2 (nbx_reduce_mx6.cc)
-ncclResult_t reduceMultiWideMx6(void* const* dsts, void* const* dstScales, int nDsts, const void* const* srcs,
-                                const void* const* srcScales, int nSrcs, size_t count, ncclDataType_t srcType,
-                                ncclDataType_t dstType, nbxDevRedOpFull op, int nPreOpSrcs, ncclStream_t stream);
 int typeSize(int dt);             // bytes of an ncclDataType_t, -1 unknown (nbx_reduce.cc)
 
 // ---- launch policy, device and stream helpers (nbx_policy.cc) ----
@@ -109,7 +101,7 @@ enum LaunchFamily {
   kFamBatch = 13, kFamBatchList = 14,   // batched buckets: flags bits kLaunchSegsShift.. = buckets of the launch
   kFamWideBatchList = 15,               // the same for nbxReduceMultiWideBatch (bit 1: fp32 output)
   kFamWideShiftedLds = 16,              // wide realigning LDS-DMA (kWideShiftedLds)
-  kFamMxBlocks = 17, kFamMxGeneric = 18,  // nbxReduceMultiWideMx: block kernel (kMxBlocks), any alignment (kMxGeneric)
+  kFamMxBlocks = 17, kFamMxGeneric = 18,  // nbxReduceMultiWideMx, MXFP8: block kernel (kMxBlocks), any alignment (kMxGeneric)
   kFamMx4Blocks = 19, kFamMx4Generic = 20, // its MXFP4 forms: quad layout (kMx4Blocks), any alignment (kMx4Generic)
   kFamMxBatchList = 21,                   // nbxReduceMultiWideMxBatch's work-list launches (kMxBatchList), flags as 15
   kFamMx6Blocks = 22, kFamMx6Generic = 23 // the MXFP6 forms: a block per lane (kMx6Blocks), any alignment (kMx6Generic)

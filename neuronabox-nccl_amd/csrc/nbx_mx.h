@@ -357,12 +357,8 @@ void fillMxOut(MxSet& ms, std::integer_sequence<int, I...>, std::integer_sequenc
   constexpr int EB = (int)sizeof(typename W::Elt);
   const void* first[] = {(const void*)&kMxBlocks<W, SCALED, O, I + 1, mxUnroll(I + 1, EB), false>...};
   const void* later[] = {nullptr, (const void*)&kMxBlocks<W, SCALED, O, J + 2, mxUnroll(J + 2, EB), true>...};
-  for (int i = 0; i < kMaxKSrcs; i++) {
-    ms.blocks[O::kIndex][0][i] = first[i];
-    ms.blocks[O::kIndex][1][i] = later[i];
-  }
-  ms.generic[O::kIndex][0] = (const void*)&kMxGeneric<W, SCALED, O, false>;
-  ms.generic[O::kIndex][1] = (const void*)&kMxGeneric<W, SCALED, O, true>;
+  setMxOut(ms, O::kIndex, first, later, (const void*)&kMxGeneric<W, SCALED, O, false>,
+           (const void*)&kMxGeneric<W, SCALED, O, true>);
 }
 
 // Plain sources store MX only (their fp32 sum is nbxReduceMultiWide's);
@@ -376,7 +372,6 @@ MxSet makeMxSet() {
   fillMxOut<W, SCALED, MxOutE4M3>(ms, all, fromTwo);
   fillMxOut<W, SCALED, MxOutE5M2>(ms, all, fromTwo);
   if constexpr (SCALED) fillMxOut<W, SCALED, MxOutF32>(ms, all, fromTwo);
-  ms.eltBytes = (int)sizeof(typename W::Elt);
   ms.scaled = SCALED ? 1 : 0;
   ms.valid = 1;
   return ms;

@@ -363,29 +363,25 @@ __global__ __launch_bounds__(kBlock) void kMx4Generic(KArgs a, MxArgs x) {
 }
 
 // ---------------------------------------------------------------------------
-// Launch table of one source kind (Mx4Set, nbx_kargs.h).
+// Launch table of one source kind (MxSet, nbx_kargs.h).
 
 template <class S, bool OUT32, int... I, int... J>
-void fillMx4Out(Mx4Set& ms, std::integer_sequence<int, I...>, std::integer_sequence<int, J...>) {
+void fillMx4Out(MxSet& ms, std::integer_sequence<int, I...>, std::integer_sequence<int, J...>) {
   const void* first[] = {(const void*)&kMx4Blocks<S, OUT32, I + 1, mx4Unroll(I + 1, S::kFp4), false>...};
   const void* later[] = {nullptr, (const void*)&kMx4Blocks<S, OUT32, J + 2, mx4Unroll(J + 2, S::kFp4), true>...};
-  for (int i = 0; i < kMaxKSrcs; i++) {
-    ms.blocks[OUT32][0][i] = first[i];
-    ms.blocks[OUT32][1][i] = later[i];
-  }
-  ms.generic[OUT32][0] = (const void*)&kMx4Generic<S, OUT32, false>;
-  ms.generic[OUT32][1] = (const void*)&kMx4Generic<S, OUT32, true>;
+  setMxOut(ms, OUT32, first, later, (const void*)&kMx4Generic<S, OUT32, false>,
+           (const void*)&kMx4Generic<S, OUT32, true>);
 }
 
-// Plain sources store MXFP4 only; MXFP4 sources also store fp32.
+// Plain sources store MXFP4 only (output 0); MXFP4 sources also store fp32 (output 1).
 template <class S>
-Mx4Set makeMx4Set() {
-  Mx4Set ms{};
+MxSet makeMx4Set() {
+  MxSet ms{};
   constexpr std::make_integer_sequence<int, kMaxKSrcs> all{};
   constexpr std::make_integer_sequence<int, kMaxKSrcs - 1> fromTwo{};
   fillMx4Out<S, false>(ms, all, fromTwo);
   if constexpr (S::kFp4) fillMx4Out<S, true>(ms, all, fromTwo);
-  ms.fp4 = S::kFp4 ? 1 : 0;
+  ms.scaled = S::kFp4 ? 1 : 0;
   ms.valid = 1;
   return ms;
 }

@@ -594,36 +594,31 @@ __global__ __launch_bounds__(kBlock) void kMx6Generic(KArgs a, MxArgs x) {
 }
 
 // ---------------------------------------------------------------------------
-// Launch table of one source kind (Mx6Set, nbx_kargs.h).
+// Launch table of one source kind (MxSet, nbx_kargs.h).
 
 template <class S, class O, int OUT, int... I, int... J>
-void fillMx6Out(Mx6Set& ms, std::integer_sequence<int, I...>, std::integer_sequence<int, J...>) {
+void fillMx6Out(MxSet& ms, std::integer_sequence<int, I...>, std::integer_sequence<int, J...>) {
   constexpr bool FP6 = mx6IsFp6<S>();
   const void* first[] = {(const void*)&kMx6Blocks<S, O, I + 1, mx6Unroll(I + 1, FP6), false>...};
   const void* later[] = {nullptr, (const void*)&kMx6Blocks<S, O, J + 2, mx6Unroll(J + 2, FP6), true>...};
-  for (int i = 0; i < kMaxKSrcs; i++) {
-    ms.blocks[OUT][0][i] = first[i];
-    ms.blocks[OUT][1][i] = later[i];
-  }
-  ms.generic[OUT][0] = (const void*)&kMx6Generic<S, O, false>;
-  ms.generic[OUT][1] = (const void*)&kMx6Generic<S, O, true>;
+  setMxOut(ms, OUT, first, later, (const void*)&kMx6Generic<S, O, false>, (const void*)&kMx6Generic<S, O, true>);
 }
 
 // Plain sources store either MXFP6 type (output 0 E2M3, 1 E3M2); MXFP6 sources
 // store their own type (output 0) or fp32 (output 1).
 template <class S>
-Mx6Set makeMx6Set() {
-  Mx6Set ms{};
+MxSet makeMx6Set() {
+  MxSet ms{};
   constexpr std::make_integer_sequence<int, kMaxKSrcs> all{};
   constexpr std::make_integer_sequence<int, kMaxKSrcs - 1> fromTwo{};
   if constexpr (mx6IsFp6<S>()) {
     fillMx6Out<S, typename S::Fmt, 0>(ms, all, fromTwo);
     fillMx6Out<S, Mx6OutF32, 1>(ms, all, fromTwo);
-    ms.fp6 = 1;
+    ms.scaled = 1;
   } else {
     fillMx6Out<S, Mx6E2M3, 0>(ms, all, fromTwo);
     fillMx6Out<S, Mx6E3M2, 1>(ms, all, fromTwo);
-    ms.fp6 = 0;
+    ms.scaled = 0;
   }
   ms.valid = 1;
   return ms;

@@ -1,6 +1,8 @@
-// nbx_reduce_mx.cc — host side of the MXFP8 block-scaled sums (nbx_mx.h,
-// nbxReduceMultiWideMx): their checks, the layout decision, one kernel pass
-// and the fold of > 8 sources through an fp32 partial.
+// nbx_reduce_mx.cc — host side of the block-scaled sums (nbxReduceMultiWideMx:
+// MXFP8 nbx_mx.h, MXFP4 nbx_mx4.h, MXFP6 nbx_mx6.h): the format table, the
+// checks, the layout decision, one kernel pass and the fold of > 8 sources
+// through an fp32 partial. The formats differ in the table's rows and in
+// nothing else here.
 #include <cstdio>
 #include <mutex>
 
@@ -8,16 +10,106 @@
 
 namespace nbx {
 namespace {
-// a table of its own, so nbxKernelCount and KernelSet stay as they are
 MxTable g_mx;
 std::once_flag g_mxOnce;
 
-bool isFp8(int t) { return t == (int)ncclFloat8e4m3 || t == (int)ncclFloat8e5m2; }
+// ---- the format table ----
+// What an element format's kernels share: the lanes a 32-element block takes
+// in the block kernel (2: 16-element groups, 4: 8-element groups, 1: the
+// block) and in the any-alignment kernel, the launch families, and the word
+// the launch-failure message says.
+enum MxFamilyId { kMx8, kMx4, kMx6 };
+struct MxFamily {
+  int famBlocks, famGeneric;
+  const char* word;
+  int groupsPerBlock;
+  int eltLanesPerBlock;
+};
+constexpr MxFamily kMxFamilies[] = {{kFamMxBlocks, kFamMxGeneric, "MX", 2, 32},
+                                    {kFamMx4Blocks, kFamMx4Generic, "MXFP4", 4, 16},
+                                    {kFamMx6Blocks, kFamMx6Generic, "MXFP6", 1, 8}};
 
-// Output index (MxSet::blocks) of a checked type.
-int mxOut(int dt) { return dt == (int)ncclFloat8e4m3 ? 0 : dt == (int)ncclFloat8e5m2 ? 1 : 2; }
+// One row per source kind, in MxTable's order (nbx_registry.h). A call is
+// taken exactly when a row has its source type, its source scales (there or
+// not) and its output type; destination scales go with every output but fp32.
+constexpr int kF16 = ncclFloat16, kBF16 = ncclBfloat16, kE4M3 = ncclFloat8e4m3, kE5M2 = ncclFloat8e5m2,
+              kF32 = ncclFloat32, kNoOut = -1;
+struct MxForm {
+  int fam;
+  int st;             // source type tag
+  bool scaled;        // ... with block scales
+  int opType;         // the type checkWideOp is asked about: it knows no FP4 / FP6 tag
+  int outs[kMxOuts];  // output type by MxSet::blocks index
+  int partOut;        // index of the fp32 partial that passes before the last write; kNoOut: plain
+                      // kinds, whose early passes are reduceMultiWideEx
+};
+constexpr MxForm kMxForms[kMxKinds] = {
+    {kMx8, kF16, false, kF16, {kE4M3, kE5M2, kNoOut}, kNoOut},
+    {kMx8, kBF16, false, kBF16, {kE4M3, kE5M2, kNoOut}, kNoOut},
+    {kMx8, kE4M3, false, kE4M3, {kE4M3, kE5M2, kNoOut}, kNoOut},
+    {kMx8, kE5M2, false, kE5M2, {kE4M3, kE5M2, kNoOut}, kNoOut},
+    {kMx8, kE4M3, true, kE4M3, {kE4M3, kE5M2, kF32}, 2},
+    {kMx8, kE5M2, true, kE5M2, {kE4M3, kE5M2, kF32}, 2},
+    {kMx4, kF16, false, kF16, {kTypeFp4, kNoOut, kNoOut}, kNoOut},
+    {kMx4, kBF16, false, kBF16, {kTypeFp4, kNoOut, kNoOut}, kNoOut},
+    {kMx4, kTypeFp4, true, kF16, {kTypeFp4, kF32, kNoOut}, 1},
+    {kMx6, kF16, false, kF16, {kTypeFp6E2M3, kTypeFp6E3M2, kNoOut}, kNoOut},
+    {kMx6, kBF16, false, kBF16, {kTypeFp6E2M3, kTypeFp6E3M2, kNoOut}, kNoOut},
+    {kMx6, kTypeFp6E2M3, true, kF16, {kTypeFp6E2M3, kF32, kNoOut}, 1},
+    {kMx6, kTypeFp6E3M2, true, kF16, {kTypeFp6E3M2, kF32, kNoOut}, 1},
+};
+
+// Bits of an element of a type tag (0: a tag no form names). An array of
+// `count` elements is a dense bit stream: 4 count bytes of fp32, ceil(count / 2)
+// of FP4, ceil(3 count / 4) of FP6. pointersOk asks the element's bytes of a
+// 16-bit source and an fp32 destination, 1 of everything narrower.
+int eltBits(int t) {
+  switch (t) {
+    case kF32: return 32;
+    case kF16: case kBF16: return 16;
+    case kE4M3: case kE5M2: return 8;
+    case kTypeFp6E2M3: case kTypeFp6E3M2: return 6;
+    case kTypeFp4: return 4;
+  }
+  return 0;
+}
+size_t arrayBytes(int t, size_t count) {
+  const size_t bits = (size_t)eltBits(t);
+  return count / 8 * bits + (count % 8 * bits + 7) / 8;
+}
+size_t eltAlign(int t) { return eltBits(t) >= 16 ? (size_t)eltBits(t) / 8 : 1; }
+
+// Groups (MXFP6: blocks) per lane of the block kernel's tile.
+int formUnroll(const MxForm& f, int nSrcs) {
+  switch (f.fam) {
+    case kMx8: return mxUnroll(nSrcs, eltBits(f.st) / 8);
+    case kMx4: return mx4Unroll(nSrcs, f.scaled);
+    default: return mx6Unroll(nSrcs, f.scaled);
+  }
+}
+
+// Workgroups per CU of the block kernel: the wide pack launch's rule. MXFP8
+// follows wideUnroll as that launch does; the others always run its big-tile
+// policy, a lane's loads counted in 16-byte units (an FP4 group is a quarter
+// of one, an FP6 block 1.5, a 16-bit block four).
+int formBlocksPerCU(const MxForm& f, int nSrcs, int unroll) {
+  bool big = true;
+  int loads;
+  switch (f.fam) {
+    case kMx8:
+      big = wideUnroll(nSrcs) > 1;
+      loads = nSrcs * wideUnroll(nSrcs);
+      break;
+    case kMx4: loads = f.scaled ? (nSrcs * unroll + 3) / 4 : nSrcs * unroll; break;
+    default: loads = f.scaled ? (nSrcs * unroll * 3 + 1) / 2 : nSrcs * unroll * 4; break;
+  }
+  int perCU = maxBlocksPerCU(big, loads);
+  if (big && !launchPolicyOverridden() && perCU < 2) perCU = 2;
+  return perCU;
+}
 
 struct MxCall {
+  const MxForm* f;
   const MxSet* ms;
   int out;            // MxSet::blocks index of the call's output
   bool blocks;        // the block kernel's layout, decided once per call
@@ -30,75 +122,84 @@ struct MxCall {
 
 // One pass over <= kMaxKSrcs sources. partFirst: srcs[0] is the fp32 partial;
 // the caller's sources, and their scales, then start at `first`. out: this
-// pass's output (2 = the fp32 partial of a later pass).
+// pass's output (the call's, or the form's partOut for the partial of a later pass).
 ncclResult_t launchMxPass(const MxCall& c, int out, bool partFirst, void* const* dsts, int nDsts,
                           const void* const* srcs, int nSrcs, int first, uint32_t mask) {
+  const MxForm& f = *c.f;
+  const MxFamily& fam = kMxFamilies[f.fam];
+  const bool out32 = out == f.partOut;
   KArgs a;
   fillKArgs(a, dsts, nDsts, srcs, nSrcs, c.count, c.op, mask);
   MxArgs x;
   std::memset(&x, 0, sizeof(x));
   const int slot0 = partFirst ? 1 : 0;
-  if (c.ms->scaled)
+  if (f.scaled)
     for (int s = slot0; s < nSrcs; s++) x.srcScale[s] = (const uint8_t*)c.srcScales[first + s - slot0];
-  if (out != 2)
+  if (!out32)
     for (int d = 0; d < kMaxKDsts; d++) x.dstScale[d] = (uint8_t*)c.dstScales[d < nDsts ? d : 0];
   const size_t cus = (size_t)cuCount(launchDevice(c.stream));
-  const int flags =
-      (out == 2 ? kLaunchOut32 : 0) | (partFirst ? kLaunchPartFirst : 0) | (c.ms->scaled ? kLaunchMxScaled : 0);
+  const int flags = (out32 ? kLaunchOut32 : 0) | (partFirst ? kLaunchPartFirst : 0) | (f.scaled ? kLaunchMxScaled : 0);
   void* args[] = {&a, &x};
   hipError_t err;
   if (c.blocks) {
     // the wide pack launch's grid rule over tiles of `unroll` groups per lane
-    const int unroll = mxUnroll(nSrcs, c.ms->eltBytes);
-    const bool big = wideUnroll(nSrcs) > 1;
-    int perCU = maxBlocksPerCU(big, nSrcs * wideUnroll(nSrcs));
-    if (big && !launchPolicyOverridden() && perCU < 2) perCU = 2;
-    a.nPacks = (uint64_t)(c.count / kMxBlockElts) * (kMxBlockElts / kMxGroupElts);
+    const int unroll = formUnroll(f, nSrcs);
+    const int perCU = formBlocksPerCU(f, nSrcs, unroll);
+    a.nPacks = (uint64_t)(c.count / kMxBlockElts) * fam.groupsPerBlock;
     const size_t tile = (size_t)unroll * kBlock;
     const size_t grid = cappedGrid((size_t)((a.nPacks + tile - 1) / tile), cus * (size_t)perCU);
     err = hipLaunchKernel(c.ms->blocks[out][slot0][nSrcs - 1], dim3((unsigned)grid), dim3(kBlock), args, 0, c.stream);
-    logLaunch(kFamMxBlocks, nSrcs, unroll, flags);
+    logLaunch(fam.famBlocks, nSrcs, unroll, flags);
   } else {
-    const size_t perWG = (size_t)kBlock / kMxBlockElts;
+    const size_t perWG = (size_t)kBlock / fam.eltLanesPerBlock;
     const size_t wgs = ((c.count + kMxBlockElts - 1) / kMxBlockElts + perWG - 1) / perWG;
     const size_t grid = cappedGrid(wgs, cus * (size_t)maxBlocksPerCU(false, nSrcs, /*classic=*/true));
     err = hipLaunchKernel(c.ms->generic[out][slot0], dim3((unsigned)grid), dim3(kBlock), args, 0, c.stream);
-    logLaunch(kFamMxGeneric, nSrcs, 1, flags);
+    logLaunch(fam.famGeneric, nSrcs, 1, flags);
   }
   if (err != hipSuccess) {
-    std::fprintf(stderr, "nbx: MX kernel launch failed: %s\n", hipGetErrorString(err));
+    std::fprintf(stderr, "nbx: %s kernel launch failed: %s\n", fam.word, hipGetErrorString(err));
     return ncclUnhandledCudaError;
   }
   return ncclSuccess;
 }
 
 bool aligned(const void* p, unsigned a) { return ((uintptr_t)p & (a - 1u)) == 0; }
+
+// Elements of a family's block-kernel tile for `nSrcs` sources of type st; 0
+// for a type or count the family does not take (the nbxDebugMx*TileElts hooks).
+int tileElts(int fam, int st, int nSrcs) {
+  if (nSrcs < 1 || nSrcs > kMaxKSrcs) return 0;
+  for (const MxForm& f : kMxForms)
+    if (f.fam == fam && f.st == st)
+      return formUnroll(f, nSrcs) * kBlock * (kMxBlockElts / kMxFamilies[fam].groupsPerBlock);
+  return 0;
+}
 }  // namespace
 
-// Source kind (MxTable index) of checked types.
-int mxKind(int st, bool scaled) {
-  const int plain = st == (int)ncclFloat16 ? 0 : st == (int)ncclBfloat16 ? 1 : st == (int)ncclFloat8e4m3 ? 2 : 3;
-  return scaled ? plain + 2 : plain;
-}
-
-// The four source types, Sum / PreMulSum, the scalar; scales only beside fp8
-// sources; an fp8 output with scale arrays, or fp32 without and from scaled
-// sources only.
+// The row of the format table that takes the call, and Sum / PreMulSum with
+// its scalar by the wide sum's rule.
 ncclResult_t checkMxTypes(ncclDataType_t srcType, ncclDataType_t dstType, const nbxDevRedOpFull& op, bool scaled,
-                          bool dstScaled) {
-  ncclResult_t cr = checkWideOp(srcType, srcType, op);
-  if (cr != ncclSuccess) return cr;
+                          bool dstScaled, int* kind, int* out) {
   const int st = (int)srcType, dt = (int)dstType;
-  if (scaled && !isFp8(st)) return ncclInvalidArgument;
-  if (dt == (int)ncclFloat32 ? (dstScaled || !scaled) : (!isFp8(dt) || !dstScaled)) return ncclInvalidArgument;
-  return ncclSuccess;
+  if (eltBits(dt) == 0 || dstScaled == (dt == kF32)) return ncclInvalidArgument;
+  for (int k = 0; k < kMxKinds; k++) {
+    const MxForm& f = kMxForms[k];
+    if (f.st != st || f.scaled != scaled) continue;
+    for (int o = 0; o < kMxOuts; o++)
+      if (f.outs[o] == dt) {
+        *kind = k;
+        *out = o;
+        return checkWideOp((ncclDataType_t)f.opType, (ncclDataType_t)f.opType, op);
+      }
+  }
+  return ncclInvalidArgument;
 }
 
 ncclResult_t checkMxBucket(int st, int dt, void* const* dsts, void* const* dstScales, int nDsts,
                            const void* const* srcs, const void* const* srcScales, int nSrcs, size_t count) {
-  const bool scaled = srcScales != nullptr, out32 = dt == (int)ncclFloat32;
-  const size_t eb = (size_t)typeSize(st), deb = out32 ? sizeof(float) : 1;
-  if (!pointersOk(eb, deb, dsts, nDsts, srcs, nSrcs)) return ncclInvalidArgument;
+  const bool scaled = srcScales != nullptr, out32 = dt == kF32;
+  if (!pointersOk(eltAlign(st), eltAlign(dt), dsts, nDsts, srcs, nSrcs)) return ncclInvalidArgument;
   for (int s = 0; scaled && s < nSrcs; s++)
     if (srcScales[s] == nullptr) return ncclInvalidArgument;
   for (int d = 0; !out32 && d < nDsts; d++)
@@ -108,15 +209,16 @@ ncclResult_t checkMxBucket(int st, int dt, void* const* dsts, void* const* dstSc
   // that source's; everything else a destination owns is apart from
   // everything a source owns, and its two arrays from each other.
   const size_t nScales = (count + kMxBlockElts - 1) / kMxBlockElts;
+  const size_t sBytes = arrayBytes(st, count), dBytes = arrayBytes(dt, count);
   for (int d = 0; d < nDsts; d++) {
-    if (!out32 && overlaps(dsts[d], count * deb, dstScales[d], nScales)) return ncclInvalidArgument;
+    if (!out32 && overlaps(dsts[d], dBytes, dstScales[d], nScales)) return ncclInvalidArgument;
     for (int s = 0; s < nSrcs; s++) {
       const bool same = st == dt && dsts[d] == srcs[s];
-      if (!same && overlaps(dsts[d], count * deb, srcs[s], count * eb)) return ncclInvalidArgument;
+      if (!same && overlaps(dsts[d], dBytes, srcs[s], sBytes)) return ncclInvalidArgument;
       if (same && scaled && dstScales[d] != srcScales[s]) return ncclInvalidArgument;
-      if (scaled && overlaps(dsts[d], count * deb, srcScales[s], nScales)) return ncclInvalidArgument;
+      if (scaled && overlaps(dsts[d], dBytes, srcScales[s], nScales)) return ncclInvalidArgument;
       if (out32) continue;
-      if (overlaps(dstScales[d], nScales, srcs[s], count * eb)) return ncclInvalidArgument;
+      if (overlaps(dstScales[d], nScales, srcs[s], sBytes)) return ncclInvalidArgument;
       if (scaled && !same && overlaps(dstScales[d], nScales, srcScales[s], nScales)) return ncclInvalidArgument;
     }
   }
@@ -139,6 +241,13 @@ const MxTable& mxTable() {
     fillMxE5M2(g_mx);
     fillMxE4M3Scaled(g_mx);
     fillMxE5M2Scaled(g_mx);
+    fillMx4F16(g_mx);
+    fillMx4BF16(g_mx);
+    fillMx4Fp4(g_mx);
+    fillMx6F16(g_mx);
+    fillMx6BF16(g_mx);
+    fillMx6E2M3(g_mx);
+    fillMx6E3M2(g_mx);
   });
   return g_mx;
 }
@@ -151,40 +260,34 @@ NBX_EXPORT ncclResult_t nbxReduceMultiWideMx(void* const* dsts, void* const* dst
                                              const void* const* srcs, const void* const* srcScales, int nSrcs,
                                              size_t count, ncclDataType_t srcType, ncclDataType_t dstType,
                                              nbxDevRedOpFull op, int nPreOpSrcs, ncclStream_t stream) {
-  const auto fp6 = [](ncclDataType_t t) { return (int)t == kTypeFp6E2M3 || (int)t == kTypeFp6E3M2; };
-  if (fp6(srcType) || fp6(dstType))   // MXFP6: nbx_reduce_mx6.cc; a pair with NBX_FLOAT4_E2M1 is refused there
-    return reduceMultiWideMx6(dsts, dstScales, nDsts, srcs, srcScales, nSrcs, count, srcType, dstType, op, nPreOpSrcs,
-                              stream);
-  if ((int)srcType == kTypeFp4 || (int)dstType == kTypeFp4)   // MXFP4: nbx_reduce_mx4.cc
-    return reduceMultiWideMx4(dsts, dstScales, nDsts, srcs, srcScales, nSrcs, count, srcType, dstType, op, nPreOpSrcs,
-                              stream);
   // ---- checks: all of them before any device call ----
   if (!argArraysOk(dsts, nDsts, srcs, nSrcs)) return ncclInvalidArgument;
   const bool scaled = srcScales != nullptr;
-  ncclResult_t cr = checkMxTypes(srcType, dstType, op, scaled, dstScales != nullptr);
+  int kind, out;
+  ncclResult_t cr = checkMxTypes(srcType, dstType, op, scaled, dstScales != nullptr, &kind, &out);
   if (cr != ncclSuccess) return cr;
   if (count == 0) return ncclSuccess;
-  const int st = (int)srcType, dt = (int)dstType;
-  const bool out32 = dt == (int)ncclFloat32;
-  cr = checkMxBucket(st, dt, dsts, dstScales, nDsts, srcs, srcScales, nSrcs, count);
+  cr = checkMxBucket((int)srcType, (int)dstType, dsts, dstScales, nDsts, srcs, srcScales, nSrcs, count);
   if (cr != ncclSuccess) return cr;
 
   // ---- layout: the block kernel needs 16-byte element pointers and 4-byte
   // destination scale pointers (the partial, scratch or dsts[0], follows) ----
   MxCall c;
-  c.ms = &mxTable()[mxKind(st, scaled)];
-  c.out = mxOut(dt);
+  c.f = &kMxForms[kind];
+  c.ms = &mxTable()[kind];
+  c.out = out;
   c.count = count;
   c.dstScales = dstScales;
   c.srcScales = srcScales;
   c.op = wideScalarOp(op);
   c.stream = (hipStream_t)stream;
+  const bool out32 = out == c.f->partOut;
   c.blocks = mxBlockLayout(dsts, out32 ? nullptr : dstScales, nDsts, srcs, nSrcs);
   if (nPreOpSrcs < 0) nPreOpSrcs = 0;
   const bool pre = op.op == nbxDevPreMulSum;
 
   if (nSrcs <= kMaxKSrcs)
-    return launchMxPass(c, c.out, false, dsts, nDsts, srcs, nSrcs, 0, preMask(pre, nPreOpSrcs, 0, nSrcs, 0));
+    return launchMxPass(c, out, false, dsts, nDsts, srcs, nSrcs, 0, preMask(pre, nPreOpSrcs, 0, nSrcs, 0));
 
   // > 8 sources: earlier passes leave the fp32 left fold of the sources before
   // the last pass in a partial that is never narrowed — dsts[0] for an fp32
@@ -200,7 +303,7 @@ NBX_EXPORT ncclResult_t nbxReduceMultiWideMx(void* const* dsts, void* const* dst
     return foldPasses(dsts, nDsts, srcs, nSrcs, part, scratch, c.stream,
                       [&](void* const* d, int nd, const void* const* s, int n, int first, bool partFirst, bool last) {
                         const int slot0 = partFirst ? 1 : 0;
-                        return launchMxPass(c, last ? c.out : 2, partFirst, d, nd, s, n, first,
+                        return launchMxPass(c, last ? out : c.f->partOut, partFirst, d, nd, s, n, first,
                                             preMask(pre, nPreOpSrcs, first, n - slot0, slot0));
                       });
   // plain sources: all but the last 7 are nbxReduceMultiWide's fp32-output
@@ -212,18 +315,15 @@ NBX_EXPORT ncclResult_t nbxReduceMultiWideMx(void* const* dsts, void* const* dst
     const void* ps[kMaxKSrcs];
     ps[0] = part;
     for (int k = 1; k < kMaxKSrcs; k++) ps[k] = srcs[first + k - 1];
-    cr = launchMxPass(c, c.out, true, dsts, nDsts, ps, kMaxKSrcs, first,
+    cr = launchMxPass(c, out, true, dsts, nDsts, ps, kMaxKSrcs, first,
                       preMask(pre, nPreOpSrcs, first, kMaxKSrcs - 1, 1));
   }
   if (hipFreeAsync(scratch, c.stream) != hipSuccess && cr == ncclSuccess) cr = ncclUnhandledCudaError;
   return cr;
 }
 
-// Elements of the block kernel's tile for `nSrcs` sources of srcType (test
-// hook, include/nbx_debug.h); 0 for a type or count the call does not take.
-NBX_EXPORT int nbxDebugMxTileElts(ncclDataType_t srcType, int nSrcs) {
-  const int st = (int)srcType;
-  if (st != (int)ncclFloat16 && st != (int)ncclBfloat16 && !isFp8(st)) return 0;
-  if (nSrcs < 1 || nSrcs > kMaxKSrcs) return 0;
-  return mxUnroll(nSrcs, isFp8(st) ? 1 : 2) * kBlock * kMxGroupElts;
-}
+// Elements of the block kernel's tile for `nSrcs` sources of srcType, family
+// by family (test hooks, include/nbx_debug.h).
+NBX_EXPORT int nbxDebugMxTileElts(ncclDataType_t srcType, int nSrcs) { return tileElts(kMx8, (int)srcType, nSrcs); }
+NBX_EXPORT int nbxDebugMx4TileElts(ncclDataType_t srcType, int nSrcs) { return tileElts(kMx4, (int)srcType, nSrcs); }
+NBX_EXPORT int nbxDebugMx6TileElts(ncclDataType_t srcType, int nSrcs) { return tileElts(kMx6, (int)srcType, nSrcs); }

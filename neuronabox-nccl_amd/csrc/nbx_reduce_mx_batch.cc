@@ -10,7 +10,6 @@
 
 namespace nbx {
 namespace {
-// a table of its own, so MxSet, KernelSet and nbxKernelCount stay as they are
 MxBatchTable g_mxBatch;
 std::once_flag g_mxBatchOnce;
 
@@ -131,14 +130,15 @@ NBX_EXPORT ncclResult_t nbxReduceMultiWideMxBatch(const nbxReduceMxTask* tasks, 
                                                   ncclDataType_t dstType, nbxDevRedOpFull op, int nPreOpSrcs,
                                                   ncclStream_t stream) {
   // ---- checks: all of them before any device call ----
-  if ((int)srcType == kTypeFp4 || (int)dstType == kTypeFp4) return ncclInvalidArgument;   // no MXFP4 batch
   const int st = (int)srcType, dt = (int)dstType;
   const bool out32 = dt == (int)ncclFloat32;
   // scaled or plain is a property of the call; without a bucket to say which,
   // the types are checked as those of the form that takes this output
   const bool scaled = nTasks > 0 && tasks != nullptr ? tasks[0].srcScales != nullptr : out32;
-  ncclResult_t r = checkMxTypes(srcType, dstType, op, scaled, !out32);
+  int kind, out;
+  ncclResult_t r = checkMxTypes(srcType, dstType, op, scaled, !out32, &kind, &out);
   if (r != ncclSuccess) return r;
+  if (kind >= kMxFp8Kinds) return ncclInvalidArgument;   // the MXFP8 kinds (and so their outputs) alone are batched
   if (nTasks < 0 || (nTasks > 0 && tasks == nullptr)) return ncclInvalidArgument;
   bool any = false;
   for (int i = 0; i < nTasks; i++) {
@@ -184,8 +184,7 @@ NBX_EXPORT ncclResult_t nbxReduceMultiWideMxBatch(const nbxReduceMxTask* tasks, 
     lists[t.nSrcs - 1].push_back(&t);
   }
   const nbxDevRedOpFull lop = wideScalarOp(op);
-  const MxBatchSet& bs = mxBatchTable()[mxKind(st, scaled)];
-  const int out = out32 ? 2 : dt == (int)ncclFloat8e4m3 ? 0 : 1;   // MxSet::blocks' output index
+  const MxBatchSet& bs = mxBatchTable()[kind];
   const bool useList = batchListEnabled();
   for (int q = 0; q < kMaxKSrcs; q++) {
     if (lists[q].empty()) continue;

@@ -50,8 +50,16 @@ typedef WideCollSet WideCollTable[kNumTypes];
 void fillWideColl16(WideCollTable& t);
 void fillWideColl8(WideCollTable& t);
 
-// the MXFP8 block-scaled sums (nbxReduceMultiWideMx): one MxSet per source
-// kind, a unit per kind (inst_mx_*.hip)
+// the block-scaled sums (nbxReduceMultiWideMx): one MxSet per source kind, a
+// unit per kind. [index] kind, its outputs (MxSet::blocks' first index):
+//   MXFP8 (nbx_mx.h, inst_mx_*.hip), outputs 0 e4m3, 1 e5m2, 2 fp32 (scaled kinds only)
+//     [0] f16  [1] bf16  [2] e4m3  [3] e5m2 plain   [4] e4m3  [5] e5m2 with scales
+//   MXFP4 (NBX_FLOAT4_E2M1, nbx_mx4.h, inst_mx4_*.hip), outputs 0 MXFP4, 1 fp32 (MXFP4 sources only)
+//     [6] f16  [7] bf16 plain   [8] MXFP4
+//   MXFP6 (NBX_FLOAT6_E2M3 / NBX_FLOAT6_E3M2, nbx_mx6.h, inst_mx6_*.hip), outputs of the
+//   plain kinds 0 E2M3, 1 E3M2, of the MXFP6 kinds 0 their own type, 1 fp32
+//     [9] f16  [10] bf16 plain   [11] E2M3  [12] E3M2
+// The host's view of the same rows is nbx_reduce_mx.cc's format table.
 typedef MxSet MxTable[kMxKinds];
 void fillMxF16(MxTable& t);
 void fillMxBF16(MxTable& t);
@@ -59,29 +67,21 @@ void fillMxE4M3(MxTable& t);
 void fillMxE5M2(MxTable& t);
 void fillMxE4M3Scaled(MxTable& t);
 void fillMxE5M2Scaled(MxTable& t);
+void fillMx4F16(MxTable& t);
+void fillMx4BF16(MxTable& t);
+void fillMx4Fp4(MxTable& t);
+void fillMx6F16(MxTable& t);
+void fillMx6BF16(MxTable& t);
+void fillMx6E2M3(MxTable& t);
+void fillMx6E3M2(MxTable& t);
 
-// their work-list batch (nbxReduceMultiWideMxBatch, nbx_mx_batch.h): one
-// MxBatchSet per source kind, a unit per kind (inst_mxb_*.hip)
-typedef MxBatchSet MxBatchTable[kMxKinds];
+// the MXFP8 kinds' work-list batch (nbxReduceMultiWideMxBatch, nbx_mx_batch.h):
+// one MxBatchSet per kind, MxTable's first six indices, a unit per kind (inst_mxb_*.hip)
+typedef MxBatchSet MxBatchTable[kMxFp8Kinds];
 void fillMxBatchF16(MxBatchTable& t);
 void fillMxBatchBF16(MxBatchTable& t);
 void fillMxBatchE4M3(MxBatchTable& t);
 void fillMxBatchE5M2(MxBatchTable& t);
 void fillMxBatchE4M3Scaled(MxBatchTable& t);
 void fillMxBatchE5M2Scaled(MxBatchTable& t);
-
-// its MXFP4 forms (NBX_FLOAT4_E2M1, nbx_mx4.h): one Mx4Set per source kind, a
-// unit per kind (inst_mx4_*.hip)
-typedef Mx4Set Mx4Table[kMx4Kinds];
-void fillMx4F16(Mx4Table& t);
-void fillMx4BF16(Mx4Table& t);
-void fillMx4Fp4(Mx4Table& t);
-
-// its MXFP6 forms (NBX_FLOAT6_E2M3 / NBX_FLOAT6_E3M2, nbx_mx6.h): one Mx6Set per
-// source kind, a unit per kind (inst_mx6_*.hip)
-typedef Mx6Set Mx6Table[kMx6Kinds];
-void fillMx6F16(Mx6Table& t);
-void fillMx6BF16(Mx6Table& t);
-void fillMx6E2M3(Mx6Table& t);
-void fillMx6E3M2(Mx6Table& t);
 }  // namespace nbx
