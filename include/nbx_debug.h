@@ -319,6 +319,17 @@ int nbxDebugMx6TileElts(ncclDataType_t srcType, int nSrcs);
 /* Elements in one tile of nbxReduceMultiWideMxBatch's kernel (kMxBatchList):
  * 4096 for every source type and count. */
 int nbxDebugMxBatchTileElts(void);
+/* The tile of nbxReduceMultiWideMx2d's tile kernel (kMx2dTiles), the same for
+ * every source type and count: *tileRows = 32, *tileCols = 128 (either may be
+ * NULL); returns their product. The call's last pass (nbx_reduce_mx2d.cc)
+ * leaves a record of family 24 (kMx2dTiles: a workgroup per tile, a 16-element
+ * group of one row per lane) or 25 (kMx2dGeneric: any layout, a column per
+ * lane); nSrcs as for the wide families, unroll 1, flags: bit 2 the first
+ * source is the fp32 partial, bit 4 the sources carry block scales. The
+ * earlier passes of a call of more than 8 sources leave the records of
+ * nbxReduceMultiWide (plain sources: 6 / 7 / 16) or of nbxReduceMultiWideMx
+ * into fp32 (scaled sources: 17 / 18 with bit 1). */
+int nbxDebugMx2dTileShape(int* tileRows, int* tileCols);
 void nbxDebugLaunchLogReset(void);
 
 #ifdef __cplusplus

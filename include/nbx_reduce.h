@@ -387,7 +387,8 @@ ncclResult_t nbxReduceMultiWideBatchStats(const nbxReduceTask* tasks, int nTasks
  * Not provided (ncclInvalidArgument): E2M3 <-> E3M2, FP6 <-> FP8 / FP4 pairs;
  * FP6 sources without scales; fp8 sources, plain or MX, into
  * MXFP4; MXFP4 sources into MXFP8; MXFP4 sources without scales; block sizes
- * other than 32; a batched form of MXFP4 or MXFP6 (MXFP8 has one:
+ * other than 32; blocks down the columns of a 2-D bucket (MXFP8 has them:
+ * nbxReduceMultiWideMx2d); a batched form of MXFP4 or MXFP6 (MXFP8 has one:
  * nbxReduceMultiWideMxBatch), a statistics form, a form inside the
  * collectives, a host-staged form, a realigning LDS-DMA form. */
 #define NBX_FLOAT4_E2M1 ((ncclDataType_t)32)
@@ -441,6 +442,57 @@ typedef struct {
 ncclResult_t nbxReduceMultiWideMxBatch(const nbxReduceMxTask* tasks, int nTasks,
                                        ncclDataType_t srcType, ncclDataType_t dstType,
                                        nbxDevRedOpFull op, int nPreOpSrcs, ncclStream_t stream);
+
+/* 2-D form of nbxReduceMultiWideMx for MXFP8: one fold of a matrix, stored with
+ * blocks down the columns and, when asked, along the rows too — the two
+ * quantised copies a consumer keeps of a matrix it contracts along either
+ * dimension — with the sources read once.
+ * Bucket: a dense row-major rows x cols matrix; element (r, c) is flat element
+ * r * cols + c and count = rows * cols.
+ * Fold: nbxReduceMultiWideMx's over the flat bucket, bit for bit: sources
+ * widened exactly, each step one unfused fp32 multiply or add in source order
+ * with denormals kept, the PreMulSum scalar by value or by device pointer, more
+ * than 8 sources in passes through an fp32 partial that is never narrowed.
+ * Column-wise output (colDsts, colScales: required, nDsts entries each, all
+ * non-NULL): block (i, c) is rows [32 i, 32 i + 32) of column c; the last block
+ * row holds rows % 32 rows when that is not 0. colDsts[d] has the bucket's own
+ * row-major layout, one fp8 code per element; colScales[d] is row-major
+ * ceil(rows / 32) x cols, the byte of block (i, c) at i * cols + c. Scale byte
+ * and codes follow the MX output rule above unchanged: m under the amax rule,
+ * S = max(be - emax, 0), R = 2^(127 - S), each code narrow(a * R); a non-finite
+ * m gives scale byte 0xFF and unscaled narrowing.
+ * Row-wise output (rowDsts, rowScales: both NULL, or both given with nDsts
+ * non-NULL entries): block (r, j) is columns [32 j, 32 j + 32) of row r; the
+ * last block of a row holds cols % 32 columns. rowScales[d] is row-major
+ * rows x ceil(cols / 32). When cols % 32 == 0 the row-wise codes and scales
+ * are exactly nbxReduceMultiWideMx's output for count = rows * cols.
+ * Types: sources f16, bf16, e4m3 or e5m2 plain (srcScales NULL), or e4m3 / e5m2
+ * with scales; output MX e4m3 or MX e5m2 (dstType need not equal srcType).
+ * Scaled sources carry the flat 1-D scale arrays of nbxReduceMultiWideMx and
+ * require cols % 32 == 0, so a row-wise output of this function or of the 1-D
+ * one feeds straight back in; scaled sources with another cols are
+ * ncclInvalidArgument. Not provided (ncclInvalidArgument): FP4 / FP6 tags, an
+ * fp32 output, column-scaled sources, in place.
+ * Checks, every one before any device call: the type, op and scalar checks of
+ * nbxReduceMultiWideMx; nSrcs in [1, NBX_MAX_SRCS], nDsts in [1, NBX_MAX_DSTS];
+ * NULL entries; element alignment to the element size; rows * cols must not
+ * overflow size_t. rows == 0 or cols == 0 is a no-op after the type and op
+ * checks. Any overlap is ncclInvalidArgument: any written array (codes or
+ * scales, row or column) against any source array (elements or scales), and any
+ * two written arrays against each other. There is no in-place form: the
+ * any-layout kernel reads the sources twice.
+ * Every element pointer 16-byte aligned, cols % 16 == 0 and every destination
+ * scale pointer 4-byte aligned runs the tile kernel (a workgroup per 32 x 128
+ * tile, the accumulators in registers across one barrier, every source byte
+ * read once); any other layout runs a column per lane and reads the sources
+ * twice. Same bits. Stream-ordered, asynchronous and graph-capturable.
+ * Not provided: FP4 / FP6 elements, a batched form, a statistics form. */
+ncclResult_t nbxReduceMultiWideMx2d(void* const* rowDsts, void* const* rowScales,
+                                    void* const* colDsts, void* const* colScales, int nDsts,
+                                    const void* const* srcs, const void* const* srcScales, int nSrcs,
+                                    size_t rows, size_t cols,
+                                    ncclDataType_t srcType, ncclDataType_t dstType,
+                                    nbxDevRedOpFull op, int nPreOpSrcs, ncclStream_t stream);
 
 /* Host-staged form of nbxReduceMulti: sources and destinations in HOST memory
  * (pinned for full speed; pageable works), the path NCCL's NET/SHM transports

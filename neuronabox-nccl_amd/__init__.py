@@ -192,6 +192,11 @@ _SIGS = {
                              ctypes.c_size_t, ctypes.c_int, ctypes.c_int, DevRedOpFull, ctypes.c_int, ctypes.c_void_p],
     "nbxReduceMultiWideMxBatch": [ctypes.POINTER(ReduceMxTask), ctypes.c_int, ctypes.c_int, ctypes.c_int, DevRedOpFull,
                                   ctypes.c_int, ctypes.c_void_p],
+    "nbxReduceMultiWideMx2d": [ctypes.POINTER(ctypes.c_void_p), ctypes.POINTER(ctypes.c_void_p),
+                               ctypes.POINTER(ctypes.c_void_p), ctypes.POINTER(ctypes.c_void_p), ctypes.c_int,
+                               ctypes.POINTER(ctypes.c_void_p), ctypes.POINTER(ctypes.c_void_p), ctypes.c_int,
+                               ctypes.c_size_t, ctypes.c_size_t, ctypes.c_int, ctypes.c_int, DevRedOpFull, ctypes.c_int,
+                               ctypes.c_void_p],
     "nbxRedOpCreateWide": [ctypes.POINTER(ctypes.c_int), ctypes.c_int, ctypes.c_int, ctypes.c_void_p],
     "nbxSetLaunchConfig": [ctypes.c_int, ctypes.c_int],
     "nbxGetLaunchConfig": [ctypes.POINTER(ctypes.c_int), ctypes.POINTER(ctypes.c_int)],
@@ -261,6 +266,8 @@ def load_library(path: Optional[str] = None) -> ctypes.CDLL:
     lib.nbxDebugMx6TileElts.restype = ctypes.c_int
     lib.nbxDebugMxBatchTileElts.argtypes = []
     lib.nbxDebugMxBatchTileElts.restype = ctypes.c_int
+    lib.nbxDebugMx2dTileShape.argtypes = [ctypes.POINTER(ctypes.c_int), ctypes.POINTER(ctypes.c_int)]
+    lib.nbxDebugMx2dTileShape.restype = ctypes.c_int
     # test hook of the Simple transport: counters and flag words of a communicator at rest
     lib.nbxDebugSimpleState.argtypes = [ctypes.c_void_p, ctypes.POINTER(ctypes.c_uint64),
                                         ctypes.POINTER(ctypes.c_uint64), ctypes.c_size_t, ctypes.POINTER(ctypes.c_int)]
@@ -402,6 +409,8 @@ class LaunchFamily(enum.IntEnum):        # include/nbx_debug.h nbxDebugLaunchLog
     MxBatchList = 21      # nbxReduceMultiWideMxBatch launches (kMxBatchList): flags as 15, and LAUNCH_MX_SCALED
     Mx6Blocks = 22        # nbxReduceMultiWideMx's MXFP6 forms: a block per lane at the converters (kMx6Blocks)
     Mx6Generic = 23       # ... any alignment, four elements (three bytes) per lane (kMx6Generic)
+    Mx2dTiles = 24        # nbxReduceMultiWideMx2d: a workgroup per 32 x 128 tile, both copies from registers (kMx2dTiles)
+    Mx2dGeneric = 25      # ... any layout, a column per lane, the sources read twice (kMx2dGeneric)
 
 
 LAUNCH_DYNAMIC, LAUNCH_OUT32, LAUNCH_PART_FIRST = 1, 2, 4
@@ -528,6 +537,37 @@ def reduce_multi_wide_mx(dsts: Sequence[int], dst_scales: Optional[Sequence[int]
 def mx_tile_elts(src_type: int, n_srcs: int) -> int:
     """Elements per tile of nbxReduceMultiWideMx's block kernel (nbxDebugMxTileElts)."""
     return int(load_library().nbxDebugMxTileElts(int(src_type), int(n_srcs)))
+
+
+def reduce_multi_wide_mx2d_raw(row_dsts: Optional[Sequence[int]], row_scales: Optional[Sequence[int]],
+                               col_dsts: Sequence[int], col_scales: Optional[Sequence[int]], srcs: Sequence[int],
+                               src_scales: Optional[Sequence[int]], rows: int, cols: int, src_type: int, dst_type: int,
+                               op: DevRedOpFull, n_pre_op_srcs: int = 0, stream: int = 0) -> int:
+    """Call nbxReduceMultiWideMx2d (a list of None is the NULL array; nDsts is len(col_dsts)); returns the code."""
+    return load_library().nbxReduceMultiWideMx2d(_ptr_array(row_dsts), _ptr_array(row_scales), _ptr_array(col_dsts),
+                                                 _ptr_array(col_scales), len(col_dsts or ()), _ptr_array(srcs),
+                                                 _ptr_array(src_scales), len(srcs), int(rows), int(cols),
+                                                 int(src_type), int(dst_type), op, int(n_pre_op_srcs),
+                                                 ctypes.c_void_p(int(stream)))
+
+
+def reduce_multi_wide_mx2d(row_dsts: Optional[Sequence[int]], row_scales: Optional[Sequence[int]],
+                           col_dsts: Sequence[int], col_scales: Sequence[int], srcs: Sequence[int],
+                           src_scales: Optional[Sequence[int]], rows: int, cols: int, src_type: int, dst_type: int,
+                           op: DevRedOpFull, n_pre_op_srcs: int = 0, stream: int = 0) -> None:
+    """reduce_multi_wide_mx over a row-major rows x cols bucket, stored as MXFP8 with 32-element blocks down
+    the columns (`col_dsts`, and `col_scales` of ceil(rows / 32) x cols bytes) and, when `row_dsts` and
+    `row_scales` (rows x ceil(cols / 32) bytes) are given, along the rows too: one read of the sources
+    for both copies. MXFP8 forms only; `src_scales` (flat 1-D blocks) need cols % 32 == 0; never in place."""
+    _check(reduce_multi_wide_mx2d_raw(row_dsts, row_scales, col_dsts, col_scales, srcs, src_scales, rows, cols,
+                                      src_type, dst_type, op, n_pre_op_srcs, stream), "nbxReduceMultiWideMx2d")
+
+
+def mx2d_tile_shape() -> tuple:
+    """(rows, columns) of the tile of nbxReduceMultiWideMx2d's tile kernel (nbxDebugMx2dTileShape)."""
+    tr, tc = ctypes.c_int(0), ctypes.c_int(0)
+    load_library().nbxDebugMx2dTileShape(ctypes.byref(tr), ctypes.byref(tc))
+    return tr.value, tc.value
 
 
 def mx6_tile_elts(src_type: int, n_srcs: int) -> int:

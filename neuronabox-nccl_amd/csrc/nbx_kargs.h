@@ -189,6 +189,32 @@ inline void setMxOut(MxSet& ms, int out, const void* const* first, const void* c
   ms.generic[out][1] = genericPart;
 }
 
+// Its 2-D form (nbx_mx2d.h, nbxReduceMultiWideMx2d): a row-major rows x cols
+// bucket stored with blocks down the columns and, when asked, along the rows
+// too. The tile kernel's workgroup owns kMx2dTileRows x kMx2dTileCols elements,
+// a lane one 16-element group of one row; a wave of the any-layout kernel owns
+// kMx2dTileRows x kMx2dWaveCols, a lane one column. KArgs.dst holds the
+// column-wise destinations; everything else 2-D travels in Mx2dArgs.
+constexpr int kMx2dTileRows = kMxBlockElts;
+constexpr int kMx2dTileCols = (kBlock / kMx2dTileRows) * kMxGroupElts;   // 8 groups: 128
+constexpr int kMx2dWaveCols = 64;
+struct Mx2dArgs {
+  const uint8_t* srcScale[kMaxKSrcs];   // scaled sources only (flat 1-D blocks); slot 0 unused behind a partial
+  uint8_t* colScale[kMaxKDsts];         // ceil(rows / 32) x cols
+  void* rowDst[kMaxKDsts];              // rowOut only
+  uint8_t* rowScale[kMaxKDsts];         // rowOut only: rows x ceil(cols / 32)
+  uint64_t rows, cols;
+  int32_t rowOut;                       // uniform: the row-wise copy is stored too
+  int32_t pad;
+};
+// Launch table of one MXFP8 source kind: [output 0 e4m3, 1 e5m2][source 0 is
+// an fp32 partial][nSrcs-1]; the any-layout kernel takes nSrcs at run time.
+struct Mx2dSet {
+  const void* tiles[2][2][kMaxKSrcs];
+  const void* generic[2][2];
+  int valid;
+};
+
 // Its work-list batch (nbx_mx_batch.h, nbxReduceMultiWideMxBatch):
 // kMxBatchList takes BatchListArgs as it is and one tile shape for every
 // source type and count — one group per lane, kBlock groups, 128 blocks. A

@@ -104,10 +104,11 @@ enum LaunchFamily {
   kFamMxBlocks = 17, kFamMxGeneric = 18,  // nbxReduceMultiWideMx, MXFP8: block kernel (kMxBlocks), any alignment (kMxGeneric)
   kFamMx4Blocks = 19, kFamMx4Generic = 20, // its MXFP4 forms: quad layout (kMx4Blocks), any alignment (kMx4Generic)
   kFamMxBatchList = 21,                   // nbxReduceMultiWideMxBatch's work-list launches (kMxBatchList), flags as 15
-  kFamMx6Blocks = 22, kFamMx6Generic = 23 // the MXFP6 forms: a block per lane (kMx6Blocks), any alignment (kMx6Generic)
+  kFamMx6Blocks = 22, kFamMx6Generic = 23, // the MXFP6 forms: a block per lane (kMx6Blocks), any alignment (kMx6Generic)
+  kFamMx2dTiles = 24, kFamMx2dGeneric = 25 // nbxReduceMultiWideMx2d: 32 x 128 tiles (kMx2dTiles), any layout (kMx2dGeneric)
 };
 // kLaunchStats: the STATS form of a wide family (6 / 7 / 15 / 16) ran
-// kLaunchMxScaled: the sources of an MX family (17 - 23) carry block scales
+// kLaunchMxScaled: the sources of an MX family (17 - 25) carry block scales
 enum LaunchFlag { kLaunchDynamic = 1, kLaunchOut32 = 2, kLaunchPartFirst = 4, kLaunchStats = 8, kLaunchMxScaled = 16 };
 void logLaunch(int family, int nSrcs, int unroll, int flags);
 

@@ -85,32 +85,39 @@ __device__ __forceinline__ uint32_t mxRowShl(uint32_t v) {
   return (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, 0x100 + N, 0xf, 0xf, false);
 }
 
+// The fold of element idx (of source block b): every source widened, scaled
+// and pre-multiplied, one fp32 add per further source in source order.
+template <class W, bool SCALED, bool PART>
+__device__ __forceinline__ float mxFoldElt(const KArgs& a, const uint8_t* const (&ss)[kMaxKSrcs], float sc, int nSrcs,
+                                           uint64_t idx, uint64_t b) {
+  using E = typename W::Elt;
+  float acc = 0.0f;
+#pragma unroll
+  for (int s = 0; s < kMaxKSrcs; s++) {
+    if (s < nSrcs) {
+      float v;
+      if (PART && s == 0) {
+        v = ((const float*)a.src[0])[idx];
+      } else {
+        v = W::wide(((const E*)a.src[s])[idx]);
+        if constexpr (SCALED) v = v * mxScaleIn(ss[s][b]);
+        if ((a.preMask >> s) & 1u) v = v * sc;
+      }
+      acc = s == 0 ? v : acc + v;
+    }
+  }
+  return acc;
+}
+
 // One element of block b per lane: i < len lanes hold element 32 b + i, the
 // others nothing (len = 0: an idle half wave). Called by whole waves,
 // converged; the two halves of a wave may hold different blocks.
 template <class W, bool SCALED, class O, bool PART>
 __device__ __forceinline__ void mxEltLane(const KArgs& a, const MxArgs& x, float sc, int nSrcs, uint64_t b, int i,
                                           int len) {
-  using E = typename W::Elt;
   const bool on = i < len;
   const uint64_t idx = b * kMxBlockElts + (uint64_t)i;
-  float acc = 0.0f;
-  if (on) {
-#pragma unroll
-    for (int s = 0; s < kMaxKSrcs; s++) {
-      if (s < nSrcs) {
-        float v;
-        if (PART && s == 0) {
-          v = ((const float*)a.src[0])[idx];
-        } else {
-          v = W::wide(((const E*)a.src[s])[idx]);
-          if constexpr (SCALED) v = v * mxScaleIn(x.srcScale[s][b]);
-          if ((a.preMask >> s) & 1u) v = v * sc;
-        }
-        acc = s == 0 ? v : acc + v;
-      }
-    }
-  }
+  const float acc = on ? mxFoldElt<W, SCALED, PART>(a, x.srcScale, sc, nSrcs, idx, b) : 0.0f;
   if constexpr (O::kF32) {
     if (on) {
 #pragma unroll
@@ -168,6 +175,44 @@ __device__ __forceinline__ void mxLoadTile(u32x4 (&part)[U][4], u32x4 (&v)[NSRC]
       for (int k = 0; k < NPK; k++) v[s][u][k] = ldPack(src[s] + (g + (uint64_t)u * kBlock) * NPK + k);
 }
 
+// The fold of group u of a tile already in registers: 16 fp32 accumulators as
+// 8 pairs, every step one unfused multiply or add in source order.
+template <class W, bool SCALED, int NSRC, int U, bool PART, bool PRE>
+__device__ __forceinline__ void mxFoldAcc(const u32x4 (&part)[U][4], const u32x4 (&v)[NSRC][U][16 / W::kEPP],
+                                          const uint32_t (&e)[NSRC][U], const float (&mul)[NSRC], int u,
+                                          f32x2 (&acc)[8]) {
+  constexpr int NPK = 16 / W::kEPP, NP = W::kEPP / 2;
+#pragma unroll
+  for (int s = 0; s < NSRC; s++) {
+    f32x2 t[8];
+    if (PART && s == 0) {
+#pragma unroll
+      for (int j = 0; j < 4; j++) {
+        t[2 * j] = f32x2{__uint_as_float(part[u][j].x), __uint_as_float(part[u][j].y)};
+        t[2 * j + 1] = f32x2{__uint_as_float(part[u][j].z), __uint_as_float(part[u][j].w)};
+      }
+    } else {
+#pragma unroll
+      for (int k = 0; k < NPK; k++)
+#pragma unroll
+        for (int w = 0; w < 4; w++) W::wideWord(v[s][u][k][w], &t[k * NP + w * W::kWP]);
+      if constexpr (SCALED) {
+        const float xs = mxScaleIn(e[s][u]);
+        const f32x2 m = {xs, xs};
+#pragma unroll
+        for (int k = 0; k < 8; k++) t[k] = t[k] * m;
+      }
+      if constexpr (PRE) {
+        const f32x2 m = {mul[s], mul[s]};
+#pragma unroll
+        for (int k = 0; k < 8; k++) t[k] = t[k] * m;
+      }
+    }
+#pragma unroll
+    for (int k = 0; k < 8; k++) acc[k] = s == 0 ? t[k] : acc[k] + t[k];
+  }
+}
+
 // Fold U groups already in registers, scale and store them. mul: as
 // wideFoldStore's (the scalar or 1.0 per source, PRE only). GATHER: all 64
 // lanes of the wave are here with full blocks, and each step's 32 scale bytes
@@ -177,39 +222,10 @@ __device__ __forceinline__ void mxFoldStore(const u32x4 (&part)[U][4], const u32
                                             const uint32_t (&e)[NSRC][U], const float (&mul)[NSRC],
                                             u32x4* const (&dst)[kMaxKDsts], uint8_t* const (&ds)[kMaxKDsts],
                                             int nDsts, uint64_t g) {
-  constexpr int NPK = 16 / W::kEPP, NP = W::kEPP / 2;
 #pragma unroll
   for (int u = 0; u < U; u++) {
     f32x2 acc[8];
-#pragma unroll
-    for (int s = 0; s < NSRC; s++) {
-      f32x2 t[8];
-      if (PART && s == 0) {
-#pragma unroll
-        for (int j = 0; j < 4; j++) {
-          t[2 * j] = f32x2{__uint_as_float(part[u][j].x), __uint_as_float(part[u][j].y)};
-          t[2 * j + 1] = f32x2{__uint_as_float(part[u][j].z), __uint_as_float(part[u][j].w)};
-        }
-      } else {
-#pragma unroll
-        for (int k = 0; k < NPK; k++)
-#pragma unroll
-          for (int w = 0; w < 4; w++) W::wideWord(v[s][u][k][w], &t[k * NP + w * W::kWP]);
-        if constexpr (SCALED) {
-          const float xs = mxScaleIn(e[s][u]);
-          const f32x2 m = {xs, xs};
-#pragma unroll
-          for (int k = 0; k < 8; k++) t[k] = t[k] * m;
-        }
-        if constexpr (PRE) {
-          const f32x2 m = {mul[s], mul[s]};
-#pragma unroll
-          for (int k = 0; k < 8; k++) t[k] = t[k] * m;
-        }
-      }
-#pragma unroll
-      for (int k = 0; k < 8; k++) acc[k] = s == 0 ? t[k] : acc[k] + t[k];
-    }
+    mxFoldAcc<W, SCALED, NSRC, U, PART, PRE>(part, v, e, mul, u, acc);
     const uint64_t q = g + (uint64_t)u * kBlock;
     if constexpr (O::kF32) {
 #pragma unroll

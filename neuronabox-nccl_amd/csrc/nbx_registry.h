@@ -84,4 +84,14 @@ void fillMxBatchE4M3(MxBatchTable& t);
 void fillMxBatchE5M2(MxBatchTable& t);
 void fillMxBatchE4M3Scaled(MxBatchTable& t);
 void fillMxBatchE5M2Scaled(MxBatchTable& t);
+
+// the MXFP8 kinds' 2-D form (nbxReduceMultiWideMx2d, nbx_mx2d.h): one Mx2dSet
+// per kind, the same six indices, a unit per kind (inst_mx2d_*.hip)
+typedef Mx2dSet Mx2dTable[kMxFp8Kinds];
+void fillMx2dF16(Mx2dTable& t);
+void fillMx2dBF16(Mx2dTable& t);
+void fillMx2dE4M3(Mx2dTable& t);
+void fillMx2dE5M2(Mx2dTable& t);
+void fillMx2dE4M3Scaled(Mx2dTable& t);
+void fillMx2dE5M2Scaled(Mx2dTable& t);
 }  // namespace nbx
