@@ -32,22 +32,36 @@ def sources(oracle, st, scaled, count, nsrc):
     return (a[0] + b[0])[:nsrc], (a[1] + b[1])[:nsrc] if scaled else None
 
 
-def run_2d(nbx, oracle, torch, kind, dt, rows, cols, nsrc, row_out=True, family=FAM_TILES, ndst=1, src_off=0, cs_off=0,
-           devop=SUM, arg=0, npre=0):
-    """One call on seeded inputs, checked: both copies, the guard bytes, the last launch record."""
-    st, scaled = kind
-    n = rows * cols
-    srcs, scales = sources(oracle, st, scaled, n, nsrc)
+def expected_2d(oracle, srcs, scales, st, dt, rows, cols, row_out=True, devop=SUM, arg=0, npre=0):
+    """{"col": (codes rows x cols, scales ceil(rows / 32) x cols), "row": (codes, scales rows x ceil(cols / 32))}
+    of the flat fp32 fold, quantised down the columns and (row_out) along the rows."""
     fold = reference(oracle, srcs, scales, st, F32, devop, arg, npre)[0].reshape(rows, cols)
     col_codes, col_scales = blocks_along_rows(oracle, np.ascontiguousarray(fold.T), dt)
     exp = {"col": (np.ascontiguousarray(col_codes.T), np.ascontiguousarray(col_scales.T))}
     if row_out:
         exp["row"] = blocks_along_rows(oracle, fold, dt)
+    return exp
+
+
+def run_2d(nbx, oracle, torch, kind, dt, rows, cols, nsrc, row_out=True, family=FAM_TILES, ndst=1, src_off=0, cs_off=0,
+           devop=SUM, arg=0, npre=0, rs_off=0, given=None, staged=None):
+    """One call, checked: both copies, the guard bytes, the last launch record. The inputs are the seeded ones, or
+    `given` = (sources, scale arrays or None) as host arrays; `staged` = (source buffers, scale buffers or None)
+    are Dev buffers that already hold `given` and are passed as they are. rs_off / cs_off: the row / column scale
+    arrays' byte offset in their allocation."""
+    st, scaled = kind
+    n = rows * cols
+    srcs, scales = given if given is not None else sources(oracle, st, scaled, n, nsrc)
+    assert len(srcs) == nsrc and all(s.size == n for s in srcs) and (scales is not None) == scaled
+    exp = expected_2d(oracle, srcs, scales, st, dt, rows, cols, row_out, devop, arg, npre)
     dev = Dev(torch)
-    sb = [dev.buf(s.nbytes, src_off if k == nsrc - 1 else 0, s) for k, s in enumerate(srcs)]   # src_off: the last source's
-    ssb = [dev.buf(e.size, 0, e) for e in scales] if scaled else None
-    out = {w: ([dev.buf(n) for _ in range(ndst)], [dev.buf(e[1].size, cs_off if w == "col" else 0) for _ in range(ndst)])
-           for w, e in exp.items()}
+    if staged is not None:
+        sb, ssb = staged
+    else:
+        sb = [dev.buf(s.nbytes, src_off if k == nsrc - 1 else 0, s) for k, s in enumerate(srcs)]   # src_off: the last source's
+        ssb = [dev.buf(e.size, 0, e) for e in scales] if scaled else None
+    out = {w: ([dev.buf(n) for _ in range(ndst)],
+               [dev.buf(e[1].size, cs_off if w == "col" else rs_off) for _ in range(ndst)]) for w, e in exp.items()}
     ptrs = lambda bs: [Dev.ptr(b) for b in bs] if bs else None
     row = out.get("row", (None, None))
     nbx.launch_log_reset()
@@ -62,6 +76,8 @@ def run_2d(nbx, oracle, torch, kind, dt, rows, cols, nsrc, row_out=True, family=
             assert np.array_equal(got, exp[w][1].reshape(-1)), (w, np.flatnonzero(got != exp[w][1].reshape(-1))[:8])
     for b in sb + (ssb or []) + [b for codes, scl in out.values() for b in codes + scl]:
         assert Dev.guards_intact(b), "bytes around a buffer were written"
+    for b, s in zip(sb + (ssb or []), list(srcs) + list(scales or [])):
+        assert np.array_equal(Dev.read(b, np.uint8), s.view(np.uint8).reshape(-1)), "a source was written"
     count, log = nbx.launch_log()
     last = log[-1]
     assert last[0] == family and last[1] == min(nsrc, 8), last
